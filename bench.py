@@ -2,6 +2,23 @@
 """bench.py -- device-resident batched TCP checksum on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|...]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what `value` needs: it builds the config's batches,
+settles and warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given and prints the line (the driver's fields, `roofline`
+from the same K launches, `settle`, `devices`).  --full adds every other
+measurement described below (`one_arena`, `e2e`, `cpu_baseline`, the keys of the
+other configs, `c1`); --no-cpu-baseline, --no-e2e and --no-extras take single
+ones out of a --full run again.
+
+--dump-outputs DIR writes what the timed path handed its caller in the last
+timed step as DIR/<name>.npy (float32): `results` (the u16 checksums or u8
+verdicts), and for the ops that write more the `fields` / `images` / `headers`
+they stored.  An array of more than DUMP_MAX_ELEMS elements is cut to a fixed,
+seeded sample of its elements, so the files stay under 64 MB.  The inputs are
+generated from fixed seeds: two runs with the same arguments dump the outputs
+of identical inputs.
 
 A step = one pass of the hot path (one tcpck_batch_* CHECKSUM launch) over one
 batch of synthetic segments already resident in HBM; consecutive steps take
@@ -23,16 +40,16 @@ ONE JSON line with the driver's fields plus:
                 (profiles/pmc_summary.json) when they were captured on the
                 very libtcpck.so loaded (sha256 stamp), else null with the
                 reason in traffic_source
-  c3, c4        (default C2 run only) BASELINE configs[2] and [3] timed the same
+  c3, c4        (--full C2 run only) BASELINE configs[2] and [3] timed the same
                 way in the same process, after C2: each rank its own batch
-  fill,         (default C2 run only) the SURVEY §8f rows timed the same way:
+  fill,         (--full C2 run only) the SURVEY §8f rows timed the same way:
   fill_noout,   send-side FILL on C2's layout with and without a results
   fill_c3,      buffer (the reference's call shape) and on C3's mix; C2 in
   c2_rfc,       RFC 1071 mode; VERIFY and RECEIVE (verdicts + host-order
   slots,        headers) on a 1M-slot receive ring, the send stream cut into
   receive,      checksummed MSS images; each with its own metric
   segment
-  c5_strong     (default C2 run only) BASELINE configs[4]: ONE 8M x 1492-B batch
+  c5_strong     (--full C2 run only) BASELINE configs[4]: ONE 8M x 1492-B batch
                 split over the N ranks with shard_range (8M images on one GPU
                 at N=1, 1M per GPU at N=8); value = all ranks' bytes / the
                 slowest rank's wall time per step, kernel_GiBs = / the slowest
@@ -84,7 +101,7 @@ CONFIGS = {
            "fixed", 8 << 20, 1492),
 }
 STRONG = {"c5"}  # configs whose total work is fixed as N grows; the rest are per-GPU (weak)
-# the other BASELINE configs, then the §8f ops, timed inside the default (C2) run, and their keys in its line
+# the other BASELINE configs, then the §8f ops, timed inside the --full C2 run, and their keys in its line
 # (the big C3 / C4 arenas last: C5 timed after C3/C4 had allocated and freed 19 GB ran 2.5 % slower
 # than in a process of its own -- 1.737 vs 1.695 ms, profiles/r03/c5_order_probe.log; in this order
 # every config matches its own process within 1 %, profiles/r03/bench_order_probe.log)
@@ -124,6 +141,8 @@ IMAGE_BYTES = {"slots": "96/608/1492 in 2048-B slots", "receive": "96/608/1492 i
 MODES = {"c2_rfc": 1}  # TCPCK_MODE_RFC1071; every other config runs the reference arithmetic (0)
 NO_RESULTS = {"fill_noout"}  # steps that write no results array (only the fields in place)
 ARENAS = 2  # identical batches taken in turn by every step (Workload; --arenas)
+DUMP_MAX_ELEMS = 4 << 20  # --dump-outputs: elements kept per array (float32: 16 MB; at most three arrays)
+DUMP_SEED = 20240  # the sample of a larger array: the same element positions in every run
 
 
 def log(*a):
@@ -139,7 +158,12 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline time budget (7 passes)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-e2e", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="default run: skip the c3/c4/c5_strong keys")
+    p.add_argument("--no-extras", action="store_true", help="--full C2 run: skip the c3/c4/c5_strong keys")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what `value` does not need: one_arena, e2e, cpu_baseline and, in the C2 run, "
+                        "the other configs' keys and c1")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32)")
     p.add_argument("--settle-ms", type=float, default=250.0,
                    help="untimed back-to-back launches before the warm-up steps (clock ramp)")
     p.add_argument("--arenas", type=int, default=ARENAS,
@@ -298,6 +322,7 @@ class Workload:
         self.extra_bytes = 0  # algorithmic bytes per launch beyond the image bytes read (+2 per result)
         self.layout = None
         self.arena = None
+        self.d_off = self.hdr_out = None  # kept for outputs(): the device offset list, RECEIVE's header array
         # Every step reads one of n_arenas identical batches, taken in turn
         # (--arenas, default ARENAS): step k+1 never finds the lines step k left
         # in the 256-MB Infinity Cache -- a sender or receiver never sees the
@@ -322,6 +347,7 @@ class Workload:
                                   min_len=lmin, max_len=lmax, sorted=True, stream=stream)
             else:
                 hdr_out = torch.empty(count * 32, dtype=torch.uint8, device="cuda")
+                self.hdr_out = hdr_out
                 self.extra_bytes = 32 * count  # the header array written
 
                 def run(a, out):
@@ -369,6 +395,7 @@ class Workload:
             img_bytes = int(ln.astype(np.int64).sum())
             lmin, lmax = int(ln.min()), int(ln.max())  # host-side layout hint, computed once
             self.layout = (off, ln)
+            self.d_off = d_off
 
             def make():
                 a = torch.empty(total, dtype=torch.uint8, device="cuda")
@@ -410,6 +437,48 @@ class Workload:
         import torch
         res = self.out.cpu().numpy()
         return res.view(np.uint16) if self.out.dtype == torch.int16 else res
+
+    def outputs(self) -> dict:
+        """What the last step handed its caller, as device tensors: `results`
+        and what the op stored beside them (FILL: the checksum `fields`, bytes
+        28-29 of every image, and the `images` they sit in; RECEIVE: the
+        `headers`; SEGMENT: the `images`)."""
+        import torch
+        last = self.bufs[(self.turn - 1) % self.n_arenas]
+        out = {"results": self.out} if self.results_written else {}
+        if self.kind == "fill":
+            out["fields"] = last.view(self.count, self.L)[:, 28:30]
+            out["images"] = last
+        elif self.kind == "fill_var":
+            at = self.d_off.to(torch.int64) + 28
+            out["fields"] = torch.stack((last[at], last[at + 1]), 1)
+            out["images"] = last
+        elif self.kind == "receive":
+            out["headers"] = self.hdr_out
+        elif self.kind == "segment":
+            out["images"] = last[1]
+        return out
+
+
+def dump_outputs(w: Workload, out_dir: str, rank: int) -> None:
+    """--dump-outputs: every array of w.outputs() as out_dir/<name>.npy
+    (float32; `_rank<r>` appended on ranks above 0).  An array of more than
+    DUMP_MAX_ELEMS elements is cut to the elements at DUMP_MAX_ELEMS positions
+    drawn once from DUMP_SEED (sorted, the same in every run)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in w.outputs().items():
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            at = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), DUMP_MAX_ELEMS))
+            flat = flat[torch.from_numpy(at).to(flat.device)]
+        host = flat.cpu().numpy()
+        if host.dtype == np.int16:  # the u16 results live in an int16 tensor
+            host = host.view(np.uint16)
+        path = os.path.join(out_dir, name + (f"_rank{rank}" if rank else "") + ".npy")
+        np.save(path, host.astype(np.float32))
+        log(f"dumped {path}: {host.size} of {t.numel()} elements")
 
 
 def measure(w: Workload, args, world, stream, coll_dev):
@@ -605,7 +674,7 @@ def main():
     stream = torch.cuda.current_stream()
     w = Workload(args.config, ctx, stream, rank, world, args.arenas)
     one_arena = None
-    if w.n_arenas > 1:
+    if args.full and w.n_arenas > 1:
         # the same K steps on ONE batch re-read step after step, for reference:
         # the Infinity Cache then serves part of each step (never `value`; timed
         # first so that a kernel trace's last K launches are `value`'s)
@@ -616,12 +685,15 @@ def main():
         w.n_arenas = k
     tmax, launch_ms, launch_ms_all, step_bytes, settle = measure(w, args, world, stream, coll_dev)
     value = step_bytes * args.steps / tmax / GIB
-    res = w.results()  # checksum results of this rank (the CPU baseline compares them)
+    if args.dump_outputs:
+        dump_outputs(w, args.dump_outputs, rank)
+    # checksum results of this rank (the e2e leg and the CPU baseline compare them)
+    res = w.results() if args.full else None
 
     # End to end through PCIe (never `value`): every rank at once, so the
     # driver's N-GPU runs also record the host-memory path's aggregate rate
     e2e = None
-    if not args.no_e2e and w.kind == "fixed" and not w.strong and w.mode == 0:
+    if args.full and not args.no_e2e and w.kind == "fixed" and not w.strong and w.mode == 0:
         if world > 1:
             dist.barrier()
         dt, ok = e2e_seconds(ctx, w.arena, res, w.count, w.L)
@@ -633,7 +705,8 @@ def main():
                            f"all {world} rank(s) at once, whole-job bytes / slowest rank; match: results == the "
                            "device path's"}
 
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and w.kind in ("fixed", "mixed")
+    want_cpu = (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+                and w.kind in ("fixed", "mixed"))
     cpu_rec = cpu_baseline_for(w, args.cpu_seconds) if want_cpu else None  # before the extras free the arena
     rec = {
         "metric": metric_for(w.kind, w.mode), "value": round(value, 2), "unit": "GiB/s", "n_gpus": world,
@@ -657,8 +730,8 @@ def main():
     del w
     torch.cuda.empty_cache()
 
-    # The other BASELINE configs, driver-timed in the same process (default run only)
-    if args.config == "c2" and not args.no_extras:
+    # The other BASELINE configs, driver-timed in the same process (--full C2 run only)
+    if args.full and args.config == "c2" and not args.no_extras:
         for name, key in EXTRAS:
             k, r = extra_config(name, key, ctx, stream, rank, world, args, coll_dev)
             rec[k] = r
@@ -666,7 +739,7 @@ def main():
         rec["cpu_baseline"] = cpu_rec
     if e2e is not None:
         rec["e2e"] = e2e
-    if rank == 0 and world == 1 and args.config == "c2" and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and args.config == "c2" and not args.no_extras:
         rec["c1"] = run_c1(20000)  # BASELINE configs[0], host CPU only
     if rank == 0:
         line, detail = compact_line(rec)

@@ -53,6 +53,20 @@ def test_pmc_traffic_belongs_to_the_loaded_library(tmp_path, monkeypatch):
     assert got is None and "no PMC pass" in note
 
 
+def test_full_and_dump_outputs_are_opt_in(monkeypatch):
+    """A plain `--gpus 1 --steps K --warmup W` run measures `value` alone: the
+    other measurements wait for --full, the output files for --dump-outputs DIR."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.gpus, a.steps, a.warmup, a.config) == (1, 7, 2, "c2")
+    assert a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "some/dir"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "some/dir"
+    # a dump stays under 64 MB: float32, at most three arrays (results, fields / headers, images) of DUMP_MAX_ELEMS
+    assert 3 * 4 * bench.DUMP_MAX_ELEMS <= 64 << 20
+
+
 def test_metric_per_kind():
     for n, _ in bench.EXTRAS:
         kind = bench.CONFIGS[n][1] if n in bench.CONFIGS else bench.EXTRA[n][1]
