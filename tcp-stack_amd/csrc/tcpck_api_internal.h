@@ -3,10 +3,11 @@
 // and their measurement twins (tcpck_ex_probe.hip in libtcpck_probe.so).  Not
 // installed.
 //
-// The router (tcpck::api::batch_*_ex) is the product's kernel policy and
-// nothing else; the probe library passes it a Hooks value to reach the
-// measured alternatives (header pass forms, fused headers on explicit kernels),
-// the product library always passes Hooks{}.
+// The router (tcpck::api::batch_*_ex) plans each batch (tcpck_plan.h: the
+// product's kernel policy and nothing else) and launches the plan; the probe
+// library passes it a Hooks value to reach the measured alternatives (header
+// pass forms, fused headers on explicit kernels), the product library always
+// passes Hooks{}.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 #include <mutex>
 
 #include "tcpck.h"
+#include "tcpck_plan.h"
 
 struct tcpck_ctx {
   int device = 0;
@@ -94,20 +96,7 @@ namespace api {
 constexpr uint64_t kScratchImages = 8ull << 20;  // 16 MiB of u16 results: C5's 8M images in one chunk
 constexpr uint64_t kScratchRetry = 64;           // out-less FILLs between allocation attempts after a refusal
 
-// Measurement hooks (libtcpck_probe.so only; the product passes Hooks{}).
-struct Hooks {
-  bool fuse_any_hdr = false;     // RECEIVE, explicit kernel: fuse the headers into any kernel that can
-                                 // (sstream's after-the-verdicts conversion, HDR 1)
-  bool hdr_after = false;        // RECEIVE into a header array: the separate header pass after VERIFY (the
-                                 // product runs it first under AUTO, tcpck_api.hip fixed_receive_fuses)
-  bool hdr_first_explicit = false;  // ... first with an explicit VERIFY kernel too (the product runs it after
-                                    // an explicit kernel, so a rejected choice leaves the header array as it was)
-  uint32_t hdr_store_bits = 0;   // HeaderArgs::store_bits of the header pass
-  bool patch_reverse = false;    // FILL's field pass in reverse image order (PatchArgs::reverse)
-  int fill_pipe = -1;            // pipelined FILL chunks: -1 AUTO's rule, 0 / 1 off, K > 1 K chunks
-  bool pipe_one_stream = false;  // ... every chunk's passes on the caller's stream (the chunking cost alone)
-};
-
+// (the measurement hooks, Hooks: tcpck_plan.h)
 // probe library: tcpck_batch_*_ex param bit selecting Hooks::patch_reverse
 constexpr int kProbeParamPatchReverse = 1 << 27;
 
@@ -142,7 +131,8 @@ int check_receive(const tcpck_ctx *ctx, int mode, const void *d_arena, uint64_t 
                   const uint64_t *d_offsets, const uint32_t *d_lengths, uint64_t count, const uint8_t *d_ok,
                   const void *d_hdr);
 
-// The routed launches behind them (device already selected, arguments valid).
+// The routed launches behind them (device already selected, arguments valid):
+// plan_fixed / plan_var, then the plan's launches.
 hipError_t run_fixed(tcpck_ctx *ctx, int op, int mode, uint8_t *arena, uint64_t stride, uint32_t len, uint64_t count,
                      void *out, int kernel, int param, hipStream_t s, uint8_t *hdr, const Hooks &hk);
 hipError_t run_var(tcpck_ctx *ctx, int op, int mode, uint8_t *arena, const uint64_t *off, const uint32_t *len,

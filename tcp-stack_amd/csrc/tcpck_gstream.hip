@@ -240,7 +240,7 @@ hipError_t by_len_np(int op, const GroupStreamArgs &a, uint32_t num_cus, hipStre
 
 hipError_t launch_np(int op, int variant, const GroupStreamArgs &b, uint32_t num_cus, hipStream_t stream) {
   switch (variant & ~4) {
-    // AUTO's variants (tcpck_api.hip run_fixed_impl: FILL of 48-240 B)
+    // AUTO's variants (tcpck_plan.cc pick_fixed: FILL of 48-240 B)
     case 0: return by_len_np<4>(op, b, num_cus, stream);
     case 0x80: return by_len_np<4, 0>(op, b, num_cus, stream);
     case 0x401: return op == kFill ? by_len_np<8, 2, 2>(op, b, num_cus, stream) : hipErrorInvalidValue;
@@ -255,12 +255,6 @@ hipError_t launch_np(int op, int variant, const GroupStreamArgs &b, uint32_t num
 
 }  // namespace
 
-bool gstream_applies(const uint8_t *arena, uint64_t stride, uint32_t len) {
-  const bool pow2 = (len & (len - 1)) == 0;
-  return stride == len && len >= 32 && len <= 1024 && (len & 15u) == 0 && (pow2 || len <= 240) &&
-         (reinterpret_cast<uintptr_t>(arena) & 15u) == 0;
-}
-
 hipError_t launch_gstream(int op, int variant, const GroupStreamArgs &a, uint32_t num_cus, hipStream_t stream) {
   if (!gstream_applies(a.arena, a.len, a.len)) return hipErrorInvalidValue;
   if (a.count == 0) return hipSuccess;
@@ -268,7 +262,7 @@ hipError_t launch_gstream(int op, int variant, const GroupStreamArgs &a, uint32_
   b.order = (variant & 4) ? dev::kOrderDefault : 4u;  // XCD-chunked order, groups of 16 blocks
   if (variant & ~0xFF7) return hipErrorInvalidValue;
   if (a.len & (a.len - 1)) return launch_np(op, variant, b, num_cus, stream);
-  // AUTO's variants (tcpck_api.hip run_fixed_impl): 0 (FILL of 512 B-1 KiB),
+  // AUTO's variants (tcpck_plan.cc pick_fixed): 0 (FILL of 512 B-1 KiB),
   // kGstreamDefaultLoads (FILL <= 256 B), kGstreamWriteBack (FILL <= 128 B)
   switch (variant & ~4) {
     case 0: return by_len<4>(op, b, num_cus, stream);

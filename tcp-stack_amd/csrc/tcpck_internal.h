@@ -6,27 +6,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tcpck_plan.h"
+
 namespace tcpck {
 
 enum Op : int { kChecksum = 0, kFill = 1, kVerify = 2 };
 enum Mode : int { kRef = 0, kRfc1071 = 1 };
 
-// ---- seg kernel: any layout, G lanes per image, U loads of 16 B in flight ----
-enum SegShape : int {
-  kShapeSmall = 0,   // G = 8,  U = 2  : images up to ~256 B
-  kShapeMss = 1,     // G = 16, U = 6  : images up to ~4 KiB (Ethernet MSS)
-  kShapeJumbo = 2,   // G = 64, U = 4  : 4-6 KiB images
-  kShapeWave2 = 3,   // G = 64, U = 2  : tuning
-  kShapeG32 = 4,     // G = 32, U = 3  : tuning
-  kShapeG4 = 5,      // G = 4,  U = 8  : tuning
-  kShapeW4 = 6,      // 4 waves per image, U = 4  : jumbo images
-  kShapeW8 = 7,      // 8 waves per image, U = 4  : jumbo images
-  kShapeW16 = 8,     // 16 waves per image, U = 2 : jumbo images
-  kShapeW16U4 = 9,   // 16 waves per image, U = 4 : tuning
-  kShapeW2 = 10,     // 2 waves per image, U = 4  : jumbo images
-  kNumShapes = 11
-};
-
+// ---- seg kernel: any layout, G lanes per image, U loads of 16 B in flight
+// (SegShape and shape_for_len: tcpck_plan.h) ----
 struct SegArgs {
   uint8_t *arena;            // image bytes (device)
   const uint64_t *offsets;   // variable layout: byte offset of image k (device)
@@ -42,7 +30,6 @@ struct SegArgs {
                              // wrapping (0: from chunk 0) -- concurrent blocks at different offsets
 };
 
-SegShape shape_for_len(uint64_t typical_len);
 hipError_t launch_seg(int op, int mode, bool fixed, SegShape shape, const SegArgs &a,
                       uint32_t num_cus, hipStream_t stream);
 
@@ -96,7 +83,6 @@ struct GroupStreamArgs {
   uint64_t per_wave; // step split, set by the launcher: steps = per_wave * waves + rem
   uint64_t rem;
 };
-bool gstream_applies(const uint8_t *arena, uint64_t stride, uint32_t len);
 // variant: 0 = 4 steps in flight, 1 = 8, 2 = 2; + 4: default block order
 // (else XCD-chunked, groups of 16 blocks); kGstreamDefaultLoads: 4 in flight,
 // loads with the default cache policy instead of nt (AUTO for FILL <= 256 B);
@@ -106,8 +92,6 @@ bool gstream_applies(const uint8_t *arena, uint64_t stride, uint32_t len);
 // FILL only: 0x400 / 0x800 / 0xC00 every chunk written back whole with the
 // nt / default / sc1 store policy (U4), kGstreamWriteBack: nt, U8 (AUTO for
 // FILL <= 128 B)
-constexpr int kGstreamDefaultLoads = 0x80;
-constexpr int kGstreamWriteBack = 0x401;
 hipError_t launch_gstream(int op, int variant, const GroupStreamArgs &a, uint32_t num_cus, hipStream_t stream);
 
 // ---- rstream (fixed stride == len): one run per wave, scalar boundary walk.
@@ -129,7 +113,6 @@ hipError_t launch_rvstream(int op, int variant, const RunArgs &a, uint32_t num_c
 // scattered (else XCD-chunked); + 16 (with a.hdr): the stream read with the
 // default cache policy.  a.hdr (VERIFY only): the run's headers in host order
 // to the dense array after its verdicts (tcpck_batch_receive).  a.oversub: 0 = by size; a.total_bytes: image bytes hint.
-bool sstream_fixed_applies(uint64_t stride, uint32_t len);
 hipError_t launch_sstream(int op, int variant, bool fixed, const RunArgs &a, uint32_t num_cus, hipStream_t stream);
 // ---- segment (tcpck_segment.hip): send stream -> checksummed images ------
 struct SegmentArgs {

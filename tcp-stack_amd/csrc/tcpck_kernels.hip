@@ -232,19 +232,6 @@ hipError_t dispatch_mode(int mode, int op, bool fixed, const SegArgs &a, uint32_
 
 }  // namespace
 
-// Images above 4 KiB: W waves per image, one block round (W x 4 KiB) just
-// covering the image (scripts/xcd_probe.py --what jumbo,
-// profiles/r01/jumbo_probe.log: 6 KiB W2 90.6%, 12 KiB W4 91.2%, 32 KiB W8
-// 90.9%, 64 KiB W16 91.1%, against 80-85% for one wave per image).
-SegShape shape_for_len(uint64_t typical_len) {
-  if (typical_len <= 256) return kShapeSmall;
-  if (typical_len <= 4096) return kShapeMss;
-  if (typical_len <= 8192) return kShapeW2;
-  if (typical_len <= 16384) return kShapeW4;
-  if (typical_len <= 32768) return kShapeW8;
-  return kShapeW16;
-}
-
 hipError_t launch_seg(int op, int mode, bool fixed, SegShape shape, const SegArgs &a,
                       uint32_t num_cus, hipStream_t stream) {
   switch (shape) {

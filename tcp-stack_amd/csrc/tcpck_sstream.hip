@@ -618,10 +618,6 @@ hipError_t dispatch(int op, const SSArgs &a, uint32_t m, uint64_t min_waves, uin
 
 }  // namespace
 
-bool sstream_fixed_applies(uint64_t stride, uint32_t len) {
-  return stride >= len && len >= 2 && (stride & 15u) == 0 && stride <= (1u << 24);
-}
-
 hipError_t launch_sstream(int op, int variant, bool fixed, const RunArgs &r, uint32_t num_cus, hipStream_t stream) {
   if (r.count == 0) return hipSuccess;
   SSArgs a{};

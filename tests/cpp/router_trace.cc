@@ -1,0 +1,484 @@
+// router_trace.cc -- the batch router's launches, recorded without a GPU.
+//
+// The router (tcpck::api::run_fixed / run_var, tcpck_api.hip + tcpck_plan.cc)
+// makes no HIP runtime call between its entry points and the tcpck::launch_*
+// functions, so this program links the router's objects with a recording
+// stand-in for every launcher of tcpck_internal.h and walks a fixed matrix of
+// requests through it on a fake context (num_cus = 256).  Each case is one
+// line: the inputs, the launches with every field of their argument structs
+// (pointers as offsets from this program's buffers), the returned hipError_t.
+//
+// Output (tests/golden/router_trace.txt, compared by tests/test_router_trace.py):
+//   F ... / V ...   one case of a fixed layout / an offset list, printed for a
+//                   small subset (`detailed` below);
+//   D ...           one group of the full matrix: the number of its cases and
+//                   the FNV-1a hash of ALL their lines, printed or not.
+// The full cartesian product of the layout axes is ~470,000 cases of 150-350
+// bytes, ~100 MB of text; the D lines keep every one of them under check in a
+// fixture small enough to commit and to read.  When a D line differs,
+// `router_trace --all` prints every case on both trees for a plain diff.
+//
+//   router_trace            the trace (the golden file)
+//   router_trace --all      every case's line
+//   router_trace --time     10^6 run_fixed AUTO FILL calls of the C2 shape
+//                           (1M x 1492-B packed images), recording off: ns per call
+//
+// Regenerating tests/golden/router_trace.txt: the file defines the router's
+// behaviour and was generated with the router's logic as it was before the
+// plan / launch split -- tcpck_api.hip of the parent of the commit that
+// introduced this program, which builds against this tree's headers:
+//   git show <that parent>:tcp-stack_amd/csrc/tcpck_api.hip > tcp-stack_amd/csrc/tcpck_api.hip
+//   make -C tcp-stack_amd trace && tests/cpp/build/router_trace > tests/golden/router_trace.txt
+//   git checkout tcp-stack_amd/csrc/tcpck_api.hip
+// A change of the router that changes a line is a change of behaviour: extend
+// the matrix and regenerate on that old logic first, and only then change the
+// router.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cinttypes>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "tcpck.h"
+#include "tcpck_tuning.h"
+#include "tcpck_internal.h"
+#include "tcpck_api_internal.h"
+
+namespace {
+
+// the harness's buffers: never read or written, only pointed into
+alignas(64) uint8_t g_arena[64];
+alignas(64) uint8_t g_out[64];
+alignas(64) uint8_t g_hdr[64];
+alignas(64) uint64_t g_off[8];
+alignas(64) uint32_t g_len[16];
+alignas(64) uint8_t g_stream[64];
+
+bool g_record = true;
+std::string g_launches;
+
+void add(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+void add(const char *fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  const int n = vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_launches.append(buf, static_cast<size_t>(std::min<int>(n, sizeof buf - 1)));
+}
+
+// a pointer as an offset from one of the buffers above (never a raw address)
+std::string P(const void *p) {
+  if (!p) return "null";
+  struct Base { const char *name; const void *at; };
+  const Base bases[] = {{"a", g_arena}, {"o", g_out}, {"h", g_hdr}, {"off", g_off}, {"len", g_len}, {"S", g_stream}};
+  const auto v = reinterpret_cast<uintptr_t>(p);
+  for (const Base &b : bases) {
+    const auto at = reinterpret_cast<uintptr_t>(b.at);
+    if (v >= at && v < at + 64) return std::string(b.name) + "+" + std::to_string(v - at);
+  }
+  return "?";
+}
+#define PS(p) P(p).c_str()
+
+}  // namespace
+
+// ---- the recording launchers -------------------------------------------------
+namespace tcpck {
+
+namespace host {
+uint64_t word_sum(const uint8_t *p, size_t n) {
+  if (g_record) add(" word_sum(p=%s n=%zu)", PS(p), n);
+  return 0;
+}
+}  // namespace host
+
+hipError_t launch_seg(int op, int mode, bool fixed, SegShape shape, const SegArgs &a, uint32_t num_cus, hipStream_t s) {
+  if (g_record)
+    add(" seg(op=%d mode=%d fixed=%d shape=%d arena=%s off=%s len=%s stride=%" PRIu64 " base=%" PRIu64 " count=%" PRIu64
+        " out=%s flen=%u os=%u order=%u rot=%u cus=%u s=%s)",
+        op, mode, fixed, static_cast<int>(shape), PS(a.arena), PS(a.offsets), PS(a.lengths), a.stride, a.base, a.count,
+        PS(a.out), a.len, a.oversub, a.order, a.rot, num_cus, PS(s));
+  return hipSuccess;
+}
+
+namespace {
+void add_run(const char *name, int op, int variant, int fixed, const RunArgs &a, uint32_t num_cus, hipStream_t s) {
+  add(" %s(op=%d v=%d fixed=%d arena=%s off=%s len=%s stride=%" PRIu64 " flen=%u base=%" PRIu64 " count=%" PRIu64
+      " out=%s os=%u tb=%" PRIu64 " bpc=%u mode=%d hdr=%s dbg=%s cus=%u s=%s)",
+      name, op, variant, fixed, PS(a.arena), PS(a.offsets), PS(a.lengths), a.stride, a.len, a.base, a.count, PS(a.out),
+      a.oversub, a.total_bytes, a.blocks_per_cu, a.mode, PS(a.hdr), PS(a.dbg), num_cus, PS(s));
+}
+}  // namespace
+
+hipError_t launch_gstream(int op, int variant, const GroupStreamArgs &a, uint32_t num_cus, hipStream_t s) {
+  if (g_record)
+    add(" gstream(op=%d v=%d arena=%s len=%u count=%" PRIu64 " out=%s os=%u order=%u pw=%" PRIu64 " rem=%" PRIu64
+        " cus=%u s=%s)",
+        op, variant, PS(a.arena), a.len, a.count, PS(a.out), a.oversub, a.order, a.per_wave, a.rem, num_cus, PS(s));
+  return hipSuccess;
+}
+
+hipError_t launch_rstream(int op, int variant, const FixedStreamArgs &a, uint32_t num_cus, hipStream_t s) {
+  if (g_record)
+    add(" rstream(op=%d v=%d arena=%s stride=%" PRIu64 " count=%" PRIu64 " out=%s dbg=%s bpc=%u os=%u pw=%" PRIu64
+        " rem=%" PRIu64 " order=%u mode=%d defer=%u side=%s snt=%u cus=%u s=%s)",
+        op, variant, PS(a.arena), a.stride, a.count, PS(a.out), PS(a.dbg), a.blocks_per_cu, a.oversub, a.per_wave, a.rem,
+        a.order, a.mode, a.defer_field, PS(a.side), a.side_nt, num_cus, PS(s));
+  return hipSuccess;
+}
+
+hipError_t launch_vvstream(int op, int variant, bool fixed, const RunArgs &a, uint32_t num_cus, hipStream_t s) {
+  if (g_record) add_run("vvstream", op, variant, fixed, a, num_cus, s);
+  return hipSuccess;
+}
+
+hipError_t launch_rvstream(int op, int variant, const RunArgs &a, uint32_t num_cus, hipStream_t s) {
+  if (g_record) add_run("rvstream", op, variant, 0, a, num_cus, s);
+  return hipSuccess;
+}
+
+hipError_t launch_sstream(int op, int variant, bool fixed, const RunArgs &a, uint32_t num_cus, hipStream_t s) {
+  if (g_record) add_run("sstream", op, variant, fixed, a, num_cus, s);
+  return hipSuccess;
+}
+
+hipError_t launch_segment(int mode, int variant, SegmentArgs a, uint32_t oversub, uint32_t num_cus, hipStream_t s) {
+  if (g_record)
+    add(" segment(mode=%d v=%d payload=%s images=%s bytes=%" PRIu64 " count=%" PRIu64 " out=%s pw=%" PRIu64
+        " rem=%" PRIu64 " seg=%u stride=%u nchunk=%u magic=%u shift=%u hdr0=%u seq0=%u order=%u os=%u cus=%u s=%s)",
+        mode, variant, PS(a.payload), PS(a.images), a.payload_bytes, a.count, PS(a.out), a.per_wave, a.rem, a.seg,
+        a.stride, a.nchunk, a.magic, a.shift, a.hdr[0], a.seq0, a.order, oversub, num_cus, PS(s));
+  return hipSuccess;
+}
+
+hipError_t launch_set_ack(int mode, const AckArgs &a, uint32_t num_cus, hipStream_t s) {
+  if (g_record)
+    add(" set_ack(mode=%d arena=%s off=%s stride=%" PRIu64 " count=%" PRIu64 " acks=%s ack=%u out=%s cus=%u s=%s)", mode,
+        PS(a.arena), PS(a.offsets), a.stride, a.count, PS(a.acks), a.ack, PS(a.out), num_cus, PS(s));
+  return hipSuccess;
+}
+
+hipError_t launch_header_swap(const HeaderArgs &a, uint32_t num_cus, hipStream_t s) {
+  if (g_record)
+    add(" header(arena=%s off=%s stride=%" PRIu64 " count=%" PRIu64 " out=%s bits=%u cus=%u s=%s)", PS(a.arena),
+        PS(a.offsets), a.stride, a.count, PS(a.out), a.store_bits, num_cus, PS(s));
+  return hipSuccess;
+}
+
+hipError_t launch_patch_fields(const PatchArgs &a, uint32_t num_cus, hipStream_t s) {
+  if (g_record)
+    add(" patch(arena=%s stride=%" PRIu64 " off=%s len=%s base=%" PRIu64 " count=%" PRIu64 " sums=%s lo=%" PRIu64
+        " hi=%" PRIu64 " update=%u packed=%u form=%u bits=%u rev=%u cus=%u s=%s)",
+        PS(a.arena), a.stride, PS(a.offsets), PS(a.lengths), a.base, a.count, PS(a.sums), a.lo, a.hi, a.update, a.packed,
+        a.probe_form, a.store_bits, a.reverse, num_cus, PS(s));
+  return hipSuccess;
+}
+
+hipError_t launch_side_copy(uint8_t *arena, uint64_t stride, uint64_t count, const uint8_t *side, const uint16_t *sums,
+                            uint32_t num_cus, hipStream_t s) {
+  if (g_record)
+    add(" side_copy(arena=%s stride=%" PRIu64 " count=%" PRIu64 " side=%s sums=%s cus=%u s=%s)", PS(arena), stride,
+        count, PS(side), PS(sums), num_cus, PS(s));
+  return hipSuccess;
+}
+
+hipError_t launch_diag_stream(int variant, const uint8_t *buf, uint64_t bytes, uint32_t *out, uint32_t num_cus,
+                              hipStream_t s) {
+  if (g_record)
+    add(" diag(v=%d buf=%s bytes=%" PRIu64 " out=%s cus=%u s=%s)", variant, PS(buf), bytes, PS(out), num_cus, PS(s));
+  return hipSuccess;
+}
+
+}  // namespace tcpck
+
+// ---- the matrix ------------------------------------------------------------
+namespace {
+
+using tcpck::api::Hooks;
+
+tcpck_ctx g_ctx;  // num_cus = 256, nothing else set
+const hipStream_t kStream = reinterpret_cast<hipStream_t>(g_stream);
+bool g_all = false;
+
+// one group of cases: a D line with the hash of every case's line
+struct Group {
+  std::string name;
+  uint64_t cases = 0, hash = 0xcbf29ce484222325ull;
+  explicit Group(std::string n) : name(std::move(n)) {}
+  void take(const std::string &line, bool detailed) {
+    ++cases;
+    for (const char c : line) hash = (hash ^ static_cast<uint8_t>(c)) * 0x100000001b3ull;
+    hash = (hash ^ '\n') * 0x100000001b3ull;
+    if (detailed || g_all) puts(line.c_str());
+  }
+  ~Group() { printf("D %s cases=%" PRIu64 " fnv=%016" PRIx64 "\n", name.c_str(), cases, hash); }
+};
+
+struct OpForm {
+  int op;
+  bool out, hdr;
+  const char *name;
+};
+const OpForm kOps[] = {{TCPCK_OP_CHECKSUM, true, false, "CHECKSUM"}, {TCPCK_OP_FILL, true, false, "FILL"},
+                       {TCPCK_OP_FILL, false, false, "FILL"},        {TCPCK_OP_VERIFY, true, false, "VERIFY"},
+                       {TCPCK_OP_RECEIVE, true, true, "RECEIVE"},    {TCPCK_OP_RECEIVE, true, false, "RECEIVE"}};
+const int kModes[] = {TCPCK_MODE_REF, TCPCK_MODE_RFC1071};
+const char *mode_name(int m) { return m == TCPCK_MODE_REF ? "REF" : "RFC"; }
+const uint64_t kCounts[] = {1, 1000};
+const int kAutoParams[] = {0, TCPCK_PARAM_RECEIVE_TWO_PASS, TCPCK_PARAM_FILL_INSTREAM, TCPCK_PARAM_FILL_UPDATE};
+
+const char *kernel_name(int k) {
+  switch (k) {
+    case TCPCK_KERNEL_AUTO: return "AUTO";
+    case TCPCK_KERNEL_SEG: return "SEG";
+    case TCPCK_KERNEL_RSTREAM: return "RSTREAM";
+    case TCPCK_KERNEL_VVSTREAM: return "VVSTREAM";
+    case TCPCK_KERNEL_GSTREAM: return "GSTREAM";
+    case TCPCK_KERNEL_SSTREAM: return "SSTREAM";
+    case TCPCK_KERNEL_RVSTREAM: return "RVSTREAM";
+    default: return "INVALID";
+  }
+}
+
+// the hooks: none, the probe library's default, those with the header pass
+// after, the field pass reversed, header store bits
+const int kNumHooks = 5;
+Hooks hooks(int i) {
+  Hooks h;
+  if (i == 1 || i == 2) h.fuse_any_hdr = h.hdr_first_explicit = true;
+  if (i == 2) h.hdr_after = true;
+  if (i == 3) h.patch_reverse = true;
+  if (i == 4) h.hdr_store_bits = 0x11;
+  return h;
+}
+
+// explicit kernels: param 0, the params AUTO gives the kernel (with the
+// deferred-FILL and header-stream bits), and the TCPCK_PARAM_* bits on top
+struct Explicit {
+  int kernel;
+  std::vector<int> params;
+};
+const std::vector<Explicit> &explicit_kernels() {
+  const int upd = TCPCK_PARAM_FILL_UPDATE, two = TCPCK_PARAM_RECEIVE_TWO_PASS, ins = TCPCK_PARAM_FILL_INSTREAM;
+  static const std::vector<Explicit> k = {
+      {TCPCK_KERNEL_RSTREAM, {0, 20, 25, 20 | upd, 20 | ins}},
+      {TCPCK_KERNEL_GSTREAM, {0, 0x80, 0x401, upd}},
+      {TCPCK_KERNEL_SSTREAM, {0, 128, 32, 32 | two, upd, two}},
+      {TCPCK_KERNEL_VVSTREAM, {0, 28, 28 | 32, 28 | 64, 28 | upd, 28 | ins}},
+      {TCPCK_KERNEL_RVSTREAM, {0, upd}},
+      {TCPCK_KERNEL_SEG, {0, 1 << 24, 1 | (1 << 24), (1 << 24) | (29 << 8), (1 << 24) | upd}},
+      {99, {0}},
+  };
+  return k;
+}
+
+void case_fixed(Group &g, const OpForm &f, int mode, uint64_t count, int align, uint32_t len, uint64_t stride,
+                int kernel, int param, int hk, bool detailed) {
+  char key[256];
+  snprintf(key, sizeof key, "F op=%s mode=%s out=%d hdr=%d n=%" PRIu64 " al=%d len=%u st=%" PRIu64 " k=%s p=0x%x hk=%d ->",
+           f.name, mode_name(mode), f.out, f.hdr, count, align, len, stride, kernel_name(kernel),
+           static_cast<unsigned>(param), hk);
+  g_launches.clear();
+  const hipError_t e = tcpck::api::run_fixed(&g_ctx, f.op, mode, g_arena + align, stride, len, count,
+                                             f.out ? g_out : nullptr, kernel, param, kStream, f.hdr ? g_hdr : nullptr,
+                                             hooks(hk));
+  g.take(std::string(key) + g_launches + " = " + std::to_string(static_cast<int>(e)), detailed);
+}
+
+struct Lay {
+  bool null;
+  uint32_t flags;
+  uint64_t typical;
+  uint32_t min_len, max_len;
+};
+
+void case_var(Group &g, const OpForm &f, int mode, uint64_t count, int align, const Lay &l, uint64_t base, int kernel,
+              int param, int hk, bool detailed) {
+  tcpck_layout lay{};
+  lay.total_bytes = l.typical * count;
+  lay.min_len = l.min_len;
+  lay.max_len = l.max_len;
+  lay.flags = l.flags;
+  const char *flags = l.null ? "null" : (l.flags == 0 ? "-" : (l.flags == 3 ? "PS" : (l.flags == 1 ? "P" : "S")));
+  char key[256];
+  snprintf(key, sizeof key,
+           "V op=%s mode=%s out=%d hdr=%d n=%" PRIu64 " al=%d lay=%s typ=%" PRIu64 " min=%u max=%u base=%" PRIu64
+           " k=%s p=0x%x hk=%d ->",
+           f.name, mode_name(mode), f.out, f.hdr, count, align, flags, l.typical, l.min_len, l.max_len, base,
+           kernel_name(kernel), static_cast<unsigned>(param), hk);
+  g_launches.clear();
+  const hipError_t e =
+      tcpck::api::run_var(&g_ctx, f.op, mode, g_arena + align, g_off, g_len, base, count, f.out ? g_out : nullptr,
+                          l.null ? nullptr : &lay, kernel, param, kStream, f.hdr ? g_hdr : nullptr, hooks(hk));
+  g.take(std::string(key) + g_launches + " = " + std::to_string(static_cast<int>(e)), detailed);
+}
+
+const uint32_t kLens[] = {2,    16,   28,   30,   32,   48,    96,    128,   144,   240,   254,    256,    258,     318,     320,
+                          322,  446,  448,  450,  510,  512,   514,   1022,  1024,  1026,  1492,   4094,   4096,    4098,    6144,
+                          8192, 9000, 16384, 24576, 24578, 32768, 49152, 65536, 65538, 131070, 131072, 1u << 24, (1u << 24) + 2};
+
+std::vector<uint64_t> strides_for(uint64_t len) {
+  const uint64_t up16 = (len & ~uint64_t{15}) + 16;  // the next multiple of 16 above len
+  // the hull edges of AUTO's gapped-layout rule (2 len, 5/4 len, 17/16 len) and one step past each
+  const uint64_t h2 = 2 * len, h54 = (5 * len / 4) & ~uint64_t{1}, h1716 = (17 * len / 16) & ~uint64_t{1};
+  std::vector<uint64_t> s = {len, len + 2, up16, up16 + 16, h2, h2 + 2, h54, h54 + 2, h1716, h1716 + 2,
+                             2048, 9216, 16384, 1u << 24, (1u << 24) + 16};
+  s.erase(std::remove_if(s.begin(), s.end(), [len](uint64_t v) { return v < len; }), s.end());
+  std::sort(s.begin(), s.end());
+  s.erase(std::unique(s.begin(), s.end()), s.end());
+  return s;
+}
+
+// the reduced lists of the explicit-kernel and hook sweeps: C2, C3-like, slot and jumbo shapes
+struct FixedShape {
+  uint32_t len;
+  uint64_t stride;
+};
+const FixedShape kReducedFixed[] = {{96, 96},     {256, 256},   {320, 320},    {512, 512},     {1024, 1024},
+                                    {1492, 1492}, {96, 256},    {254, 256},    {510, 2048},    {512, 2048},
+                                    {1492, 2048}, {9000, 9216}, {9000, 16384}, {65536, 65536}, {28, 28}};
+const Lay kReducedVar[] = {{true, 0, 0, 0, 0},       {false, 1, 96, 30, 1492},   {false, 1, 732, 30, 1492},
+                           {false, 1, 1492, 30, 1492}, {false, 1, 20000, 30, 60000}, {false, 1, 60000, 30, 131071},
+                           {false, 2, 96, 30, 254},  {false, 2, 254, 30, 254},   {false, 2, 732, 30, 1492},
+                           {false, 3, 732, 30, 1492}, {false, 0, 732, 30, 1492},  {false, 1, 732, 28, 1492}};
+
+// the printed subset of the AUTO sweeps: 1000 images, an aligned arena, no
+// param bits (FILL with a results buffer: also TCPCK_PARAM_FILL_INSTREAM)
+bool detailed_param(const OpForm &f, int param) {
+  return param == 0 || (param == TCPCK_PARAM_FILL_INSTREAM && f.op == TCPCK_OP_FILL && f.out);
+}
+
+// the shapes printed in full: both sides of the FILL forms' edges that
+// tests/test_gpu_fill_concurrent.py reads from the golden file, and one shape
+// per kernel AUTO picks
+bool detailed_fixed(uint32_t len, uint64_t stride) {
+  const FixedShape shown[] = {{96, 96},     {318, 318},   {320, 320},   {512, 512},  {1024, 1024},
+                              {1492, 1492}, {510, 2048},  {512, 2048},  {9000, 9216}};
+  for (const FixedShape &s : shown)
+    if (s.len == len && s.stride == stride) return true;
+  return false;
+}
+
+void sweep_fixed_auto() {
+  for (const OpForm &f : kOps)
+    for (const int mode : kModes) {
+      char name[128];
+      snprintf(name, sizeof name, "F op=%s mode=%s out=%d hdr=%d k=AUTO", f.name, mode_name(mode), f.out, f.hdr);
+      Group g(name);
+      for (const uint32_t len : kLens)
+        for (const uint64_t count : kCounts)
+          for (const int align : {0, 2})
+            for (const uint64_t stride : strides_for(len))
+              for (const int param : kAutoParams)
+                case_fixed(g, f, mode, count, align, len, stride, TCPCK_KERNEL_AUTO, param, 0,
+                           count == 1000 && align == 0 && mode == TCPCK_MODE_REF && detailed_param(f, param) &&
+                               ((f.op == TCPCK_OP_FILL && f.out)
+                                    ? detailed_fixed(len, stride)
+                                    : (len == 1492 && stride == 1492) || (len == 512 && stride == 2048)));
+    }
+}
+
+void sweep_var_auto() {
+  const uint64_t typicals[] = {0, 96, 254, 256, 258, 446, 448, 450, 732, 1022, 1024, 1026, 1492, 20000, 32768, 32770, 60000};
+  const uint32_t mins[] = {0, 28, 30}, maxs[] = {0, 1492, 131071, 131072};
+  for (const OpForm &f : kOps)
+    for (const int mode : kModes) {
+      char name[128];
+      snprintf(name, sizeof name, "V op=%s mode=%s out=%d hdr=%d k=AUTO", f.name, mode_name(mode), f.out, f.hdr);
+      Group g(name);
+      std::vector<Lay> lays = {{true, 0, 0, 0, 0}};
+      for (const uint64_t typical : typicals)
+        for (const uint32_t flags : {0u, 1u, 2u, 3u})
+          for (const uint32_t mn : mins)
+            for (const uint32_t mx : maxs) lays.push_back({false, flags, typical, mn, mx});
+      for (const Lay &l : lays)
+        for (const uint64_t count : kCounts)
+          for (const int align : {0, 2})
+            for (const uint64_t base : {uint64_t{0}, uint64_t{4096}})
+              for (const int param : kAutoParams) {
+                // printed: PACKED lists around the FILL forms' edges (FILL with a results buffer), else C3's 732 B
+                const bool edge = f.op == TCPCK_OP_FILL && f.out && l.flags == 1 &&
+                                  (l.typical == 446 || l.typical == 450 || l.typical == 1022 || l.typical == 1026);
+                const bool c3 = mode == TCPCK_MODE_REF && (l.flags == 1 || l.flags == 2) && l.typical == 732;
+                case_var(g, f, mode, count, align, l, base, TCPCK_KERNEL_AUTO, param, 0,
+                         count == 1000 && align == 0 && base == 0 && detailed_param(f, param) && !l.null &&
+                             l.min_len == 30 && l.max_len == 1492 && (edge || c3));
+              }
+    }
+}
+
+void sweep_explicit() {
+  for (const Explicit &k : explicit_kernels())
+    for (const OpForm &f : kOps) {
+      char name[128];
+      snprintf(name, sizeof name, "X op=%s out=%d hdr=%d k=%s", f.name, f.out, f.hdr, kernel_name(k.kernel));
+      Group g(name);
+      for (const int mode : kModes)
+        for (const int param : k.params)
+          for (const int hk : {0, 1})
+            for (const uint64_t count : kCounts) {
+              const bool detailed = count == 1000 && mode == TCPCK_MODE_REF && hk == 0 && param == k.params.back() &&
+                                    (f.hdr || (f.op == TCPCK_OP_FILL && f.out));
+              for (const FixedShape &s : kReducedFixed)
+                case_fixed(g, f, mode, count, 0, s.len, s.stride, k.kernel, param, hk,
+                           detailed && s.len == 512 && s.stride == 512);
+              for (const Lay &l : kReducedVar)
+                case_var(g, f, mode, count, 0, l, 0, k.kernel, param, hk,
+                         detailed && l.typical == 732 && l.min_len == 30 && l.flags == 1);
+            }
+    }
+}
+
+void sweep_hooks() {
+  for (int hk = 0; hk < kNumHooks; ++hk)
+    for (const OpForm &f : kOps) {
+      char name[128];
+      snprintf(name, sizeof name, "H op=%s out=%d hdr=%d k=AUTO hk=%d", f.name, f.out, f.hdr, hk);
+      Group g(name);
+      for (const int mode : kModes)
+        for (const int param : kAutoParams)
+          for (const uint64_t count : kCounts) {
+            const bool detailed = count == 1000 && mode == TCPCK_MODE_REF && param == 0 && hk >= 2 &&
+                                  (f.hdr || (f.op == TCPCK_OP_FILL && f.out));
+            for (const FixedShape &s : kReducedFixed)
+              case_fixed(g, f, mode, count, 0, s.len, s.stride, TCPCK_KERNEL_AUTO, param, hk,
+                         detailed && s.len == 512 && s.stride == 2048);
+            for (const Lay &l : kReducedVar)
+              case_var(g, f, mode, count, 0, l, 0, TCPCK_KERNEL_AUTO, param, hk,
+                       detailed && l.typical == 732 && l.min_len == 30 && l.flags == 2);
+          }
+    }
+}
+
+int time_mode() {
+  g_record = false;
+  for (int rep = 0; rep < 2; ++rep) {  // the first round warms up
+    const auto t0 = std::chrono::steady_clock::now();
+    int bad = 0;
+    for (int i = 0; i < 1000000; ++i)
+      bad += tcpck::api::run_fixed(&g_ctx, TCPCK_OP_FILL, TCPCK_MODE_REF, g_arena, 1492, 1492, 1u << 20, g_out,
+                                   TCPCK_KERNEL_AUTO, 0, kStream, nullptr, Hooks{}) != hipSuccess;
+    const double ns = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count();
+    if (bad) return 1;
+    if (rep) printf("run_fixed AUTO FILL 1048576 x 1492 B: %.1f ns per call\n", ns / 1e6);
+  }
+  return 0;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+  if (argc > 1 && !strcmp(argv[1], "--time")) return time_mode();
+  g_all = argc > 1 && !strcmp(argv[1], "--all");
+  sweep_fixed_auto();
+  sweep_var_auto();
+  sweep_explicit();
+  sweep_hooks();
+  return 0;
+}

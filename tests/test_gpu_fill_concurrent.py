@@ -12,8 +12,10 @@ compared byte-exact with the reference's insert (oracle/ref16.c restating
 include/tcp-header.h:252-263, pinned by tests/golden).
 
 Also: which out-less FILLs take a slot at all (only the forms
-that read the results back), and that a FILL captured into a HIP graph takes
-none and replays byte-exact.
+that read the results back -- on both sides of every edge of AUTO's FILL
+forms, the expectation read from the router's recorded launches,
+tests/golden/router_trace.txt), and that a FILL captured into a HIP graph
+takes none and replays byte-exact.
 """
 import threading
 
@@ -161,3 +163,87 @@ def test_fill_noout_under_graph_capture(built_lib, oracle_c):
         assert c.scratch_state() == before
     finally:
         c.close()
+
+
+def _golden_has_field_pass(key):
+    """Whether the recorded launches (tests/golden/router_trace.txt) of the
+    request `key` -- with a results buffer -- include FILL's field pass."""
+    import os
+    from conftest import ROOT
+    with open(os.path.join(ROOT, "tests", "golden", "router_trace.txt")) as f:
+        lines = [l for l in f if l.startswith(key + " ->")]
+    assert len(lines) == 1, key
+    return " patch(" in lines[0]
+
+
+def _mean_exact_lengths(count, typical, lo=30, hi=1492):
+    """count even lengths in [lo, hi] with mean exactly `typical`, minimum lo
+    and maximum hi: all `typical`, but one image of lo and one of hi, and the
+    bytes that pair is off the mean by spread over the next images."""
+    ln = np.full(count, typical, np.int64)
+    ln[0], ln[1] = lo, hi
+    k, d = 2, 2 * typical - lo - hi  # bytes still to add (d > 0) or to take away
+    while d:
+        step = min(d, hi - typical) if d > 0 else max(d, lo - typical)
+        ln[k] += step
+        d -= step
+        k += 1
+    assert ln.min() == lo and ln.max() == hi and int(ln.sum()) == count * typical and not (ln & 1).any()
+    return ln.astype(np.uint32)
+
+
+def test_scratch_exactly_where_the_plan_has_a_field_pass(built_lib, oracle_c):
+    """Both sides of every edge of AUTO's FILL forms, out-less through
+    batch_*_ex with KERNEL_AUTO, each on a fresh (probe library: scratch_state)
+    context and 4,096 images, with param 0 and TCPCK_PARAM_FILL_INSTREAM:
+    packed fixed images of 318 / 320 B (vvstream's deferred form from 320 B)
+    and 512 / 1024 B (vvstream deferred / rstream 25), 510 / 512-B images in
+    2048-B slots (sstream's deferred form from 512 B), a packed offset list of
+    typical image 446 / 450 B (the update form from 448 B), and in RFC 1071
+    mode of 1022 / 1026 B (vvstream's deferred form from 1 KiB; REF batches of
+    that size take the update form).  The arena is the oracle's FILL byte for
+    byte, and a scratch slot is used exactly when the recorded launches of the
+    same request with a results buffer have a field pass -- the expectation is
+    read from the router's golden trace, not restated here."""
+    import tcpck
+    count = 4096
+    cases = [("fixed", L, st, tcpck.MODE_REF) for L, st in
+             ((318, 318), (320, 320), (512, 512), (1024, 1024), (510, 2048), (512, 2048))]
+    cases += [("var", t, 0, tcpck.MODE_REF) for t in (446, 450)]
+    cases += [("var", t, 0, tcpck.MODE_RFC1071) for t in (1022, 1026)]
+    seen = set()
+    for kind, L, stride, mode in cases:
+        for param in (0, tcpck.PARAM_FILL_INSTREAM):
+            mname = "REF" if mode == tcpck.MODE_REF else "RFC"
+            if kind == "fixed":
+                key = f"F op=FILL mode={mname} out=1 hdr=0 n=1000 al=0 len={L} st={stride} k=AUTO p={param:#x} hk=0"
+                off = np.arange(count, dtype=np.int64) * stride
+                ln = np.full(count, L, np.uint32)
+                a = torch.zeros(count * stride, dtype=torch.uint8, device="cuda")
+                tcpck.synth_fixed(a, stride, L, count, seed=L)
+            else:
+                key = (f"V op=FILL mode={mname} out=1 hdr=0 n=1000 al=0 lay=P typ={L} min=30 max=1492 base=0 "
+                       f"k=AUTO p={param:#x} hk=0")
+                ln = _mean_exact_lengths(count, L)
+                off = np.concatenate(([0], np.cumsum(ln.astype(np.int64))[:-1]))
+                a = torch.zeros(count * L, dtype=torch.uint8, device="cuda")
+                d_off, d_ln = dev(off.astype(np.uint64)), dev(ln)
+                tcpck.synth_var(a, d_off, d_ln, 1492, count, seed=L)
+            assert a.data_ptr() % 16 == 0
+            field_pass = _golden_has_field_pass(key)
+            seen.add(field_pass)
+            want = expected_fill(host(a), off, ln, oracle_c, mode=mode)
+            c = tcpck.Context(0, probe=True)
+            try:
+                if kind == "fixed":
+                    c.batch_fixed_ex(tcpck.OP_FILL, a, stride, L, count, None, tcpck.KERNEL_AUTO, param, mode=mode)
+                else:
+                    c.batch_var_ex(tcpck.OP_FILL, a, d_off, d_ln, count, None, tcpck.KERNEL_AUTO, param, mode=mode,
+                                   total_bytes=count * L, min_len=30, max_len=1492, packed=True)
+                np.testing.assert_array_equal(host(a), want, err_msg=key)
+                alloc, used = c.scratch_state()
+                print(key, "field pass" if field_pass else "in-stream", (alloc, used))
+                assert (used != 0) == field_pass and alloc == (4 if field_pass else 0), (key, alloc, used)
+            finally:
+                c.close()
+    assert seen == {False, True}

@@ -1,6 +1,6 @@
 """AUTO FILL on packed fixed images around round 4's policy edges: vvstream's
 deferred form for 320 B - 1 KiB, gstream up to 256 B, rstream's deferred form
-from 1 KiB (tcpck_api.hip pick_fixed / run_fixed_impl; measurements in
+from 1 KiB (tcpck_plan.cc pick_fixed / plan_fixed; measurements in
 profiles/r04/fill_policy_sweep.log).
 
 Every arena byte and result against the oracle's FILL (socket-manager.cc:9-10:

@@ -712,7 +712,7 @@ def test_vvstream_rfc1071_fixed_fill(ctx, oracle_c, stride, length, count):
 
 
 # ---- seg W-wave shapes with the chunk-walk rotation (SegArgs::rot = param bits 8-15) ----
-# AUTO's C4 form (seg W16, rot 29, tcpck_api.hip kSegW16Rot): image k's chunks are
+# AUTO's C4 form (seg W16, rot 29, tcpck_plan.cc kSegW16Rot): image k's chunks are
 # read from 1-KiB step (rot k) mod (chunks / 64) on, wrapping; every byte is still
 # summed once, so results are the unrotated ones (include/tcp-header.h:252-263).
 @pytest.mark.parametrize("shape", [11, 7, 8, 9])  # W2, W4, W8, W16
