@@ -200,6 +200,72 @@ int tcpck_batch_receive(tcpck_ctx *ctx, int mode, void *d_arena, uint64_t stride
                         const uint64_t *d_offsets, const uint32_t *d_lengths, uint64_t count,
                         uint8_t *d_ok, void *d_hdr, const tcpck_layout *layout, tcpck_stream stream);
 
+/* ---- batched receive delivery: accepted payloads -> the receive stream ----
+ * The receive side's per-byte loop: SocketInternal::Accept() appends an
+ * accepted packet's payload (packet->begin()..end()) to recv_buffer_, byte by
+ * byte through a deque (include/socket-internal.h:323-334).  Here, for a batch:
+ * image k is laid out as in tcpck_batch_receive (at k * stride, `len` bytes, or
+ * at d_offsets[k], d_lengths[k] bytes; lengths even, >= 32), and for every k
+ * with d_dst[k] != TCPCK_DELIVER_SKIP
+ *     d_recv[d_dst[k], d_dst[k] + len_k - 32) := image bytes [32, len_k).
+ * Every other byte of d_recv keeps its value.  An image whose d_dst[k] is odd,
+ * or whose range does not fit in recv_bytes (or whose length or offset is odd,
+ * or whose length is below 32 or above 16 MiB), is skipped whole: no partial write
+ * and no write outside [0, recv_bytes) happens, whatever the device arrays
+ * hold.  The arena is only read.  Preconditions: the destination ranges of
+ * different images are disjoint (with overlap, which image's bytes land is
+ * unspecified); d_recv does not overlap the arena.  d_arena even; d_recv 16-B
+ * aligned; d_dst: u64[count].  d_dst comes from tcpck_plan_deliver (below) or
+ * any other source.  Asynchronous on `stream`; nothing is allocated; no host
+ * synchronisation. */
+#define TCPCK_DELIVER_SKIP UINT64_MAX
+int tcpck_batch_deliver(tcpck_ctx *ctx, const void *d_arena, uint64_t stride, uint32_t len,
+                        const uint64_t *d_offsets, const uint32_t *d_lengths, uint64_t count,
+                        const uint64_t *d_dst, void *d_recv, uint64_t recv_bytes, tcpck_stream stream);
+
+/* The host planner: which images of an arrival sequence the connection accepts
+ * and where their payloads go.  Plain host code, reentrant, no device.  It
+ * walks the images in arrival order as SocketInternal::RecvPacket
+ * (include/socket-internal.h:161-171) followed by Estab::operator()(const
+ * TcpHeader &, ...) (src/state.cc:195-223) does.  h_hdr: 32 * count bytes of
+ * host-order headers as tcpck_batch_receive writes them with d_hdr != NULL
+ * (TcpLength u16 at byte 10, seq u32 at 16, ack u32 at 20, flags at byte 25 --
+ * the reference's bits: ACK 0x08, SYN 0x40, FIN 0x80 -- window u16 at 26);
+ * h_ok: the verdicts; h_lengths: the image lengths (NULL: every image `len`);
+ * odd lengths or lengths < 32 return TCPCK_EINVAL.  Per image k:
+ *   !h_ok[k]      verdict BAD_SUM | SEND_ACK, h_ack[k] = rcv_nxt, no state
+ *                 change (TcpStateManager::InvalideCheckSum);
+ *   accepted      IsAck (ACK set, SYN and FIN clear), ack <= snd_nxt (a plain
+ *                 unsigned compare, as the reference) and seq == rcv_nxt:
+ *                 snd_una = max(ack, snd_una), rcv_nxt = seq + TcpLength (u32
+ *                 wrap), rcv_wnd = window; ACCEPT, and SEND_ACK iff TcpLength >
+ *                 0; h_ack[k] = the new rcv_nxt.  The payload is appended iff
+ *                 TcpLength > 0 and len_k > 32: PAYLOAD, h_dst[k] =
+ *                 st->delivered, delivered += len_k - 32 -- the reference
+ *                 appends begin()..end(), len_k - 32 bytes, whatever TcpLength
+ *                 says;
+ *   anything else verdict 0, h_dst[k] = TCPCK_DELIVER_SKIP, h_ack[k] = rcv_nxt.
+ * The walk stops with *consumed = k before an image that would leave Estab
+ * (its FIN branch: IsFin, ack <= snd_nxt, seq == rcv_nxt) and before a payload
+ * that does not fit in recv_bytes; images from k on get SKIP, verdict 0 and
+ * h_ack = rcv_nxt, and *st holds the state reached.  Otherwise *consumed =
+ * count.  h_dst[k] is TCPCK_DELIVER_SKIP wherever PAYLOAD is not set.
+ * TCPCK_EINVAL: st or consumed NULL; with count > 0 any other pointer but
+ * h_lengths NULL; a bad length (above); st->delivered > recv_bytes.  Nothing
+ * is written on an error. */
+typedef struct tcpck_rcv_state { /* the TcpControlBlock fields Estab reads and writes */
+  uint32_t rcv_nxt, snd_nxt, snd_una;
+  uint16_t rcv_wnd, reserved;
+  uint64_t delivered;            /* bytes appended to the receive stream so far */
+} tcpck_rcv_state;
+#define TCPCK_RCV_ACCEPT 1u   /* Estab's data/ACK branch took the image            */
+#define TCPCK_RCV_PAYLOAD 2u  /* ... and Accept() appends its payload (h_dst[k] set) */
+#define TCPCK_RCV_SEND_ACK 4u /* the reference replies SendAck(snd_nxt, h_ack[k], .) */
+#define TCPCK_RCV_BAD_SUM 8u  /* !ok: InvalideCheckSum(), Discard + SendAck           */
+int tcpck_plan_deliver(const void *h_hdr, const uint8_t *h_ok, const uint32_t *h_lengths, uint32_t len,
+                       uint64_t count, tcpck_rcv_state *st, uint64_t recv_bytes,
+                       uint64_t *h_dst, uint8_t *h_verdict, uint32_t *h_ack, uint64_t *consumed);
+
 /* ---- batched segmentation: send stream -> checksummed images -------------
  * The data-segment send path in one device pass.  The reference, per segment:
  * TcpSendingBuffer::GetAsTcpPacket(0, window) cuts the next <= window bytes

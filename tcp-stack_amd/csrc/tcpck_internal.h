@@ -133,6 +133,25 @@ struct SegmentArgs {
 // stores; + 8 default block order (else XCD-chunked).  oversub: 0 = by size
 hipError_t launch_segment(int mode, int variant, SegmentArgs a, uint32_t oversub, uint32_t num_cus,
                           hipStream_t stream);
+// ---- deliver (tcpck_deliver.hip): accepted payloads -> the receive stream ----
+// Image k at k * stride, `len` bytes (offsets == null) or at offsets[k],
+// lengths[k] bytes; its payload (bytes 32..) goes to recv[dst[k], ...) unless
+// dst[k] is TCPCK_DELIVER_SKIP, odd, or the range does not fit recv_bytes.
+struct DeliverArgs {
+  const uint8_t *arena;      // even
+  const uint64_t *offsets;   // null: fixed stride
+  const uint32_t *lengths;
+  const uint64_t *dst;       // u64[count]
+  uint8_t *recv;             // 16-B aligned
+  uint64_t stride;
+  uint64_t count;
+  uint64_t recv_bytes;
+  uint64_t per_block, rem;   // run split over the blocks, set by the launcher
+  uint32_t len;
+  uint32_t order;            // block order, set by the launcher
+};
+hipError_t launch_deliver(DeliverArgs a, uint32_t num_cus, hipStream_t stream);
+
 // ---- retransmit ACK rewrite with incremental checksum update (tcpck_resend.hip) ----
 struct AckArgs {
   uint8_t *arena;

@@ -51,6 +51,13 @@ HEADER_BYTES = 32
 LAYOUT_PACKED = 1
 LAYOUT_SORTED = 2
 
+# receive delivery (tcpck_batch_deliver / tcpck_plan_deliver)
+DELIVER_SKIP = 0xFFFFFFFFFFFFFFFF  # dst[k]: image k is not delivered
+RCV_ACCEPT = 1    # Estab's data/ACK branch took the image
+RCV_PAYLOAD = 2   # ... and Accept() appends its payload (dst[k] set)
+RCV_SEND_ACK = 4  # the reference replies SendAck(snd_nxt, ack[k], .)
+RCV_BAD_SUM = 8   # checksum failed: InvalideCheckSum(), Discard + SendAck
+
 # include/tcpck_tuning.h
 KERNEL_AUTO = 0
 KERNEL_SEG = 1    # param: seg shape + 1 (1..11, SEG_SHAPES), 0 = by length
@@ -122,6 +129,7 @@ EXPORTS = (
     "tcpck_memcpy_h2d", "tcpck_memcpy_d2h", "tcpck_stream_sync",
     "tcpck_synth_fixed", "tcpck_synth_var", "tcpck_batch_segment", "tcpck_batch_header_swap",
     "tcpck_batch_receive", "tcpck_host_batch_fixed_multi", "tcpck_host_batch_var_multi",
+    "tcpck_batch_deliver", "tcpck_plan_deliver",
 )
 
 
@@ -135,6 +143,13 @@ class Layout(ctypes.Structure):
     _fields_ = [("total_bytes", ctypes.c_uint64), ("min_len", ctypes.c_uint32),
                 ("max_len", ctypes.c_uint32), ("flags", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32)]
+
+
+class RcvState(ctypes.Structure):
+    """tcpck_rcv_state: the TcpControlBlock fields Estab reads and writes, and the
+    bytes appended to the receive stream so far."""
+    _fields_ = [("rcv_nxt", ctypes.c_uint32), ("snd_nxt", ctypes.c_uint32), ("snd_una", ctypes.c_uint32),
+                ("rcv_wnd", ctypes.c_uint16), ("reserved", ctypes.c_uint16), ("delivered", ctypes.c_uint64)]
 
 
 _libs: dict = {}
@@ -183,6 +198,9 @@ def lib(probe: bool = False) -> ctypes.CDLL:
         "tcpck_batch_receive": (i32, [vp, i32, vp, u64, u32, vp, vp, u64, vp, vp, ctypes.POINTER(Layout), vp]),
         "tcpck_batch_receive_ex": (i32, [vp, i32, vp, u64, u32, vp, vp, u64, vp, vp, ctypes.POINTER(Layout), i32, i32,
                                          vp]),
+        "tcpck_batch_deliver": (i32, [vp, vp, u64, u32, vp, vp, u64, vp, vp, u64, vp]),
+        "tcpck_plan_deliver": (i32, [vp, vp, vp, u32, u64, ctypes.POINTER(RcvState), u64, vp, vp, vp,
+                                     ctypes.POINTER(u64)]),
         # include/tcpck_tuning.h
         "tcpck_batch_fixed_ex": (i32, [vp, i32, i32, vp, u64, u32, u64, vp, i32, i32, vp]),
         "tcpck_batch_var_ex": (i32, [vp, i32, i32, vp, vp, vp, u64, vp, ctypes.POINTER(Layout), i32, i32, vp]),
@@ -283,6 +301,32 @@ def synth_var(arena, offsets, lengths, max_len: int, count: int, seed: int = 42,
                                  first_index, kind, _stream(stream)), "tcpck_synth_var")
 
 
+def plan_deliver(hdr, ok, state: RcvState, recv_bytes: int, lengths=None, length: int = 0):
+    """tcpck_plan_deliver on numpy arrays (host only, no device): hdr = 32 B of host-order header
+    per image as batch_receive writes them, ok = its verdicts, lengths (or one `length`) = the image
+    lengths.  Walks the arrival sequence as RecvPacket + Estab do (socket-internal.h:161-171,
+    state.cc:195-223), updates `state` in place and returns (dst u64[n], verdict u8[n], ack u32[n],
+    consumed): dst[k] is where batch_deliver puts image k's payload, or DELIVER_SKIP."""
+    import numpy as np
+    ok = np.ascontiguousarray(ok, dtype=np.uint8)
+    n = ok.size
+    hdr = np.ascontiguousarray(hdr, dtype=np.uint8).reshape(-1)
+    if hdr.size != 32 * n:
+        raise ValueError("hdr must hold 32 bytes per image")
+    if lengths is not None:
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        if lengths.size != n:
+            raise ValueError("lengths must hold one entry per image")
+    dst = np.empty(n, np.uint64)
+    verdict = np.empty(n, np.uint8)
+    ack = np.empty(n, np.uint32)
+    consumed = ctypes.c_uint64()
+    _check(lib().tcpck_plan_deliver(hdr.ctypes.data, ok.ctypes.data, _ptr(lengths), length, n, ctypes.byref(state),
+                                    recv_bytes, dst.ctypes.data, verdict.ctypes.data, ack.ctypes.data,
+                                    ctypes.byref(consumed)), "tcpck_plan_deliver")
+    return dst, verdict, ack, consumed.value
+
+
 # ---- context -------------------------------------------------------------------
 
 class Context:
@@ -362,6 +406,14 @@ class Context:
             _check(self._L.tcpck_batch_receive(*args, _stream(stream)), "tcpck_batch_receive")
         else:
             _check(self._L.tcpck_batch_receive_ex(*args, kernel, param, _stream(stream)), "tcpck_batch_receive_ex")
+
+    def batch_deliver(self, arena, count: int, dst, recv, recv_bytes: int, stride: int = 0, length: int = 0,
+                      offsets=None, lengths=None, stream=None) -> None:
+        """Accept()'s payload append for a batch (tcpck_batch_deliver, socket-internal.h:323-334):
+        recv[dst[k], dst[k] + len_k - 32) = bytes 32.. of image k for every k with dst[k] !=
+        DELIVER_SKIP; every other byte of recv keeps its value.  Layout as batch_receive."""
+        _check(self._L.tcpck_batch_deliver(self._h, _ptr(arena), stride, length, _ptr(offsets), _ptr(lengths), count,
+                                           _ptr(dst), _ptr(recv), recv_bytes, _stream(stream)), "tcpck_batch_deliver")
 
     def batch_segment(self, payload, payload_bytes: int, seg: int, hdr, seq0: int, images, stride: int,
                       out=None, mode: int = MODE_REF, param: int | None = None, stream=None) -> int:
