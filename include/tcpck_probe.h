@@ -87,6 +87,19 @@ int tcpck_probe_scratch_fail(tcpck_ctx *ctx, int n, uint64_t *refusals);
 #define TCPCK_PROBE_PIPE_ONE_STREAM 0x100
 int tcpck_probe_set_fill_pipe(tcpck_ctx *ctx, int k, int prio);
 
+/* tcpck_batch_deliver's launch grid for this context (tests): run > 0 replaces
+ * the launcher's images-per-block rule, max_blocks > 0 (<= 2^24) replaces its
+ * cap of 64 x the resident grid; 0, 0 restores the product's rule.  The kernel
+ * is the product's own: only the split of the batch over the blocks changes,
+ * so a few hundred images reach the paths that otherwise need 12,288 images
+ * (several images per block) or 6.3 million (several groups per block).
+ * *blocks / *per_block / *rem (each may be NULL) receive the split of the last
+ * deliver launch of this context (the first *rem blocks hold *per_block + 1
+ * images, the others *per_block; all 0 before the first launch).  Not
+ * synchronised with concurrent tcpck_batch_deliver calls on the context. */
+int tcpck_probe_set_deliver_grid(tcpck_ctx *ctx, uint64_t run, uint64_t max_blocks, uint64_t *blocks,
+                                 uint64_t *per_block, uint64_t *rem);
+
 /* Timing-only streaming micro-kernel over d_buf (results are not checksums):
  * variant = chunks per lane per step x steps in flight x scan, see
  * tcp-stack_amd/csrc/tcpck_diag.hip.  d_out: u32 per wave. */

@@ -74,6 +74,12 @@ struct tcpck_ctx {
   int probe_fill_pipe = -1;        // probe library: K (0/1 off, -1 AUTO's rule)
   bool probe_pipe_one_stream = false;  // probe library: the K chunks one after the other on the caller's stream
 
+  // probe library: deliver's launch grid (tcpck_probe_set_deliver_grid; 0: the
+  // launcher's rule) and the split of the last deliver launch, {blocks,
+  // per_block, rem}.  The product library leaves all five at 0.
+  uint64_t probe_deliver_run = 0, probe_deliver_max_blocks = 0;
+  uint64_t probe_deliver_split[3] = {0, 0, 0};
+
   // probe library only (tcpck_ex_probe.hip): per-wave time stamp buffer, and the
   // side stream + events of the concurrent RECEIVE form
   void *dbg = nullptr;

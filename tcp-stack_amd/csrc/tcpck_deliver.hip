@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(64 * W) deliver_kernel(DeliverArgs a) {
       // source offset of destination offset x of the image: delta + x
       const uint32_t delta = img_rel + 32u - d_rel;
       const uint32_t nch = cand ? ((e_rel + 15u) >> 4) - (d_rel >> 4) : 0u;
-      const uint32_t incl = dev::wave_inclusive_scan(nch);  // <= 64 x 4096 chunks
+      const uint32_t incl = dev::wave_inclusive_scan(nch);  // <= 64 x 2^20 chunks (+ 64: a range may straddle one more)
       const uint32_t excl = incl - nch;
       const uint32_t T = dev::read_lane(incl, 63);
       const uint32_t nsteps = (T + 63) >> 6;
@@ -236,7 +236,8 @@ __global__ void __launch_bounds__(64 * W) deliver_kernel(DeliverArgs a) {
 
 }  // namespace
 
-hipError_t launch_deliver(DeliverArgs a, uint32_t num_cus, hipStream_t stream) {
+hipError_t launch_deliver(DeliverArgs a, uint32_t num_cus, uint64_t run_forced, uint64_t max_blocks_forced,
+                          uint64_t *split, hipStream_t stream) {
   if (a.count == 0) return hipSuccess;
   constexpr int W = kDeliverWaves, U = 4;
   static const uint32_t per_cu = [] {
@@ -248,10 +249,14 @@ hipError_t launch_deliver(DeliverArgs a, uint32_t num_cus, hipStream_t stream) {
   // runs of up to one group (64 images) per block while that fills the device
   // four times over; a large batch gets 64 x the resident grid and longer runs
   const uint64_t resident = static_cast<uint64_t>(per_cu) * num_cus;
-  const uint64_t run = std::min<uint64_t>(64, std::max<uint64_t>(1, a.count / (resident * 4)));
-  uint64_t blocks = std::min<uint64_t>((a.count + run - 1) / run, resident * 64);
+  // (tests force either through the probe library to reach the group walk at small counts)
+  const uint64_t run =
+      run_forced ? run_forced : std::min<uint64_t>(64, std::max<uint64_t>(1, a.count / (resident * 4)));
+  const uint64_t cap = max_blocks_forced ? max_blocks_forced : resident * 64;
+  const uint64_t blocks = std::min<uint64_t>(a.count / run + (a.count % run != 0), cap);
   a.per_block = a.count / blocks;
   a.rem = a.count % blocks;
+  if (split) split[0] = blocks, split[1] = a.per_block, split[2] = a.rem;
   a.order = 4u;  // groups of 16 blocks per XCD
   hipLaunchKernelGGL((deliver_kernel<W, U>), dim3(static_cast<uint32_t>(blocks)), dim3(64 * W), 0, stream, a);
   return hipGetLastError();
@@ -287,5 +292,12 @@ extern "C" int tcpck_batch_deliver(tcpck_ctx *ctx, const void *d_arena, uint64_t
   a.len = len;
   a.count = count;
   a.recv_bytes = recv_bytes;
-  return hip_status(tcpck::launch_deliver(a, static_cast<uint32_t>(ctx->num_cus), static_cast<hipStream_t>(stream)));
+#ifdef TCPCK_PROBE  // the probe library: the grid a test set, and the split it reads back
+  return hip_status(tcpck::launch_deliver(a, static_cast<uint32_t>(ctx->num_cus), ctx->probe_deliver_run,
+                                          ctx->probe_deliver_max_blocks, ctx->probe_deliver_split,
+                                          static_cast<hipStream_t>(stream)));
+#else
+  return hip_status(tcpck::launch_deliver(a, static_cast<uint32_t>(ctx->num_cus), 0, 0, nullptr,
+                                          static_cast<hipStream_t>(stream)));
+#endif
 }

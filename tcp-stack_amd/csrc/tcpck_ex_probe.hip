@@ -11,7 +11,8 @@
 //     any kernel that can (sstream's after-the-verdicts conversion, HDR 1);
 //   * tcpck_probe_receive_ex: the header pass forms (TCPCK_PROBE_RECEIVE_*);
 //   * tcpck_ctx_set_debug, tcpck_diag_stream, tcpck_probe_scratch_state,
-//     tcpck_probe_scratch_fail, tcpck_probe_set_fill_pipe.
+//     tcpck_probe_scratch_fail, tcpck_probe_set_fill_pipe,
+//     tcpck_probe_set_deliver_grid.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -251,6 +252,18 @@ int tcpck_probe_set_fill_pipe(tcpck_ctx *ctx, int k, int prio) {
   ctx->pipe_prio = prio;
   ctx->probe_fill_pipe = k;
   ctx->probe_pipe_one_stream = one_stream;
+  return TCPCK_OK;
+}
+
+int tcpck_probe_set_deliver_grid(tcpck_ctx *ctx, uint64_t run, uint64_t max_blocks, uint64_t *blocks,
+                                 uint64_t *per_block, uint64_t *rem) {
+  // (a grid dimension is a u32; the launcher's own cap is far below this one)
+  if (!ctx || max_blocks > (1ull << 24)) return TCPCK_EINVAL;
+  if (blocks) *blocks = ctx->probe_deliver_split[0];
+  if (per_block) *per_block = ctx->probe_deliver_split[1];
+  if (rem) *rem = ctx->probe_deliver_split[2];
+  ctx->probe_deliver_run = run;
+  ctx->probe_deliver_max_blocks = max_blocks;
   return TCPCK_OK;
 }
 

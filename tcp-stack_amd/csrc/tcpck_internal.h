@@ -150,7 +150,11 @@ struct DeliverArgs {
   uint32_t len;
   uint32_t order;            // block order, set by the launcher
 };
-hipError_t launch_deliver(DeliverArgs a, uint32_t num_cus, hipStream_t stream);
+// run > 0 replaces the launcher's images-per-block rule, max_blocks > 0 its cap
+// on the grid (the product passes 0, 0; the probe library a test's values);
+// split (may be null) receives {blocks, per_block, rem} of the launch.
+hipError_t launch_deliver(DeliverArgs a, uint32_t num_cus, uint64_t run, uint64_t max_blocks, uint64_t *split,
+                          hipStream_t stream);
 
 // ---- retransmit ACK rewrite with incremental checksum update (tcpck_resend.hip) ----
 struct AckArgs {

@@ -12,6 +12,7 @@ import os
 import numpy as np
 
 SKIP = 0xFFFFFFFFFFFFFFFF
+MAX_LEN = 1 << 24  # a longer image is no TCP image: tcpck_batch_deliver skips it
 ACCEPT, PAYLOAD, SEND_ACK, BAD_SUM = 1, 2, 4, 8
 F_ACK, F_SYN, F_FIN = 0x08, 0x40, 0x80  # header byte 25, the reference's bits (tcp-header.h:122-162)
 M32 = 0xFFFFFFFF
@@ -63,13 +64,42 @@ def plan_np(hdr, ok, lengths, state, recv_bytes):
 
 
 def deliver_np(arena, offsets, lengths, dst, recv):
-    """recv (a uint8 array, changed in place and returned) after tcpck_batch_deliver:
-    odd dst and ranges that do not fit are skipped whole."""
-    for off, ln, d in zip(np.asarray(offsets).tolist(), np.asarray(lengths).tolist(), np.asarray(dst).tolist()):
+    """recv (a uint8 array, changed in place and returned) after tcpck_batch_deliver
+    (include/tcpck.h): an image whose dst is SKIP or odd, whose range does not fit, whose
+    length or offset is odd, or whose length is below 32 or above 16 MiB is skipped whole
+    (a length of 32 has no payload)."""
+    for off, ln, d in zip(np.asarray(offsets, np.uint64).tolist(), np.asarray(lengths, np.int64).tolist(),
+                          np.asarray(dst, np.uint64).tolist()):
         p = ln - 32
-        if d == SKIP or d & 1 or p <= 0 or d + p > recv.size:
+        if d == SKIP or d & 1 or ln & 1 or off & 1 or ln < 32 or ln > MAX_LEN or p <= 0 or d + p > recv.size:
             continue
         recv[d:d + p] = arena[off + 32:off + ln]
+    return recv
+
+
+def deliver_np_fast(arena, offsets, lengths, dst, recv, chunk=1 << 22):
+    """deliver_np without the per-image loop, for counts in the hundreds of thousands: the
+    delivered images' payload bytes as one gather / scatter over np.repeat'ed per-byte
+    indices, `chunk` bytes at a time.  Like the device (and unlike the loop, which lets the
+    later image win) it leaves overlapping destination ranges unspecified."""
+    off = np.asarray(offsets, np.uint64)
+    ln = np.asarray(lengths, np.int64)
+    d = np.asarray(dst, np.uint64)
+    p = ln - 32
+    size = np.uint64(recv.size)
+    ok = (d != np.uint64(SKIP)) & ((d & np.uint64(1)) == 0) & ((off & np.uint64(1)) == 0) & ((ln & 1) == 0)
+    ok &= (ln > 32) & (ln <= MAX_LEN) & (d <= size)  # (d <= size first: d + p cannot wrap below)
+    ok[ok] = d[ok] + p[ok].astype(np.uint64) <= size
+    src, at, p = off[ok].astype(np.int64) + 32, d[ok].astype(np.int64), p[ok]
+    ends = np.cumsum(p)
+    lo = 0
+    while lo < p.size:  # whole images per round, at least one
+        hi = max(lo + 1, int(np.searchsorted(ends, (ends[lo - 1] if lo else 0) + chunk, side="right")))
+        n = p[lo:hi]
+        first = np.repeat(ends[lo:hi] - n, n)   # per byte: where its image's bytes start in this round's run
+        within = np.arange((ends[lo - 1] if lo else 0), ends[hi - 1]) - first
+        recv[np.repeat(at[lo:hi], n) + within] = arena[np.repeat(src[lo:hi], n) + within]
+        lo = hi
     return recv
 
 

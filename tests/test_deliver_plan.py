@@ -181,3 +181,52 @@ def test_argument_errors(built_lib):
     assert tcpck.DELIVER_SKIP == SKIP and (tcpck.RCV_ACCEPT, tcpck.RCV_PAYLOAD, tcpck.RCV_SEND_ACK, tcpck.RCV_BAD_SUM) == (
         ACCEPT, PAYLOAD, SEND_ACK, BAD_SUM)
     assert ctypes.sizeof(tcpck.RcvState) == 24
+
+
+def _small_cases():
+    from deliver_cases import (alignment_case, guard_rails_cases, jumbo_cases, random_rule_case, scattered_case,
+                               shapes_cases)
+    cases = [alignment_case(6, 0), alignment_case(10, 2), scattered_case(), random_rule_case(4000, 71)]
+    cases += guard_rails_cases() + jumbo_cases(9000, 7) + jumbo_cases(65536, 5)
+    for layout in ("fixed", "slots", "packed"):
+        cases += shapes_cases(65, layout) + shapes_cases(257, layout)
+    return cases
+
+
+def test_deliver_np_fast_is_the_loop_form():
+    """deliver_np_fast (the vectorised form the large GPU tests compare with) byte for byte against
+    deliver_np, on the inputs of the small GPU tests and on 4000 random images of which a third
+    break one clause of the skip rule each; small `chunk` values put the round boundaries of the
+    gather inside the batch."""
+    from deliver_np import deliver_np_fast
+    cases = _small_cases()
+    rule = cases[3]
+    ln, off, d = (np.asarray(v).astype(np.uint64) for v in (rule.lengths, rule.offsets, rule.dst))
+    # every clause is present among the random images, and so are delivered ones
+    assert (ln & 1).any() and (off & 1).any() and (ln < 32).any() and (ln == 32).any() and (ln > 1 << 24).any()
+    assert ((d & 1) == 1).sum() > (d == SKIP).sum() > 0 and (d[d != SKIP] > rule.recv_bytes).any()
+    for c in cases:
+        alloc = c.recv_bytes if c.recv_alloc is None else c.recv_alloc
+        want = np.full(alloc, 0xA5, np.uint8)
+        deliver_np(c.arena, c.offsets, c.lengths, c.dst, want[:c.recv_bytes])
+        for chunk in (1 << 22, 4096, 1):
+            got = np.full(alloc, 0xA5, np.uint8)
+            deliver_np_fast(c.arena, c.offsets, c.lengths, c.dst, got[:c.recv_bytes], chunk=chunk)
+            assert np.array_equal(got, want), chunk
+    assert (want != 0xA5).any()
+
+
+def test_deliver_np_skip_rule():
+    """Each clause of include/tcpck.h's skip rule on its own, in both forms: nothing lands."""
+    from deliver_np import deliver_np_fast
+    arena = np.arange(4096, dtype=np.uint8)
+    bad = [(0, 101, 0), (1, 100, 0), (0, 30, 0), (0, 0, 0), (0, 32, 0), (0, (1 << 24) + 2, 0), (0, 0xFFFFFFFE, 0),
+           (0, 100, 1), (0, 100, SKIP), (0, 100, 190), (0, 100, (1 << 64) - 2)]
+    for form in (deliver_np, deliver_np_fast):
+        for off, ln, d in bad:
+            recv = form(arena, [off, 256], [ln, 40], [d, 100], np.full(256, 0xA5, np.uint8))
+            want = np.full(256, 0xA5, np.uint8)
+            want[100:108] = arena[288:296]
+            assert np.array_equal(recv, want), (form.__name__, off, ln, d)
+        recv = form(arena, [0], [100], [188], np.full(256, 0xA5, np.uint8))  # ends exactly at the end
+        assert np.array_equal(recv[188:], arena[32:100]) and (recv[:188] == 0xA5).all()

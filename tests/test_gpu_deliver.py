@@ -8,6 +8,8 @@ fails."""
 import numpy as np
 import pytest
 
+from deliver_cases import (alignment_case, back_to_back, guard_rails_cases, jumbo_cases, scattered_case,
+                           shapes_cases)
 from deliver_np import SKIP, DeliverGolden, deliver_np, plan_np
 
 pytestmark = pytest.mark.gpu
@@ -35,36 +37,44 @@ def host(t):
     return t.cpu().numpy()
 
 
-def check(ctx, arena, offsets, lengths, dst, recv_bytes, fixed=None, recv_alloc=None, stream=None):
+def check(ctx, arena, offsets, lengths, dst, recv_bytes, fixed=None, recv_alloc=None, stream=None, base_mis=0,
+          count=None):
     """Delivers on the device and compares the whole receive buffer (recv_alloc >= recv_bytes
-    bytes of it, the rest guard) with deliver_np; returns it."""
+    bytes of it, the rest guard) with deliver_np; returns it.  base_mis: the arena starts that
+    many bytes into its allocation.  count: only the first `count` images are the batch -- the
+    device arrays still hold them all, and the others must leave no trace."""
     offsets = np.asarray(offsets, np.uint64)
     lengths = np.asarray(lengths, np.uint32)
     dst = np.asarray(dst, np.uint64)
+    count = len(dst) if count is None else count
     recv_alloc = recv_bytes if recv_alloc is None else recv_alloc
-    d_arena = dev(arena)
+    d_arena = torch.zeros(base_mis + arena.size + (16 if base_mis else 0), dtype=torch.uint8, device="cuda")
+    d_arena = d_arena[base_mis:base_mis + arena.size]  # (a view: the allocation lives as long as it does)
+    d_arena.copy_(torch.from_numpy(np.ascontiguousarray(arena)))
     d_recv = torch.full((max(recv_alloc, 16),), FILL, dtype=torch.uint8, device="cuda")
     d_dst = dev(dst)
     torch.cuda.synchronize()  # the uploads and the fill ran on torch's stream
+    p_arena = d_arena.data_ptr() if base_mis else d_arena
     if fixed:
         stride, length = fixed
-        ctx.batch_deliver(d_arena, len(dst), d_dst, d_recv, recv_bytes, stride=stride, length=length, stream=stream)
+        ctx.batch_deliver(p_arena, count, d_dst, d_recv, recv_bytes, stride=stride, length=length, stream=stream)
     else:
         d_off, d_len = dev(offsets), dev(lengths)
         torch.cuda.synchronize()
-        ctx.batch_deliver(d_arena, len(dst), d_dst, d_recv, recv_bytes, offsets=d_off, lengths=d_len, stream=stream)
+        ctx.batch_deliver(p_arena, count, d_dst, d_recv, recv_bytes, offsets=d_off, lengths=d_len, stream=stream)
     got = host(d_recv)
     want = np.full(got.size, FILL, np.uint8)
-    deliver_np(arena, offsets, lengths, dst, want[:recv_bytes])
+    deliver_np(arena, offsets[:count], lengths[:count], dst[:count], want[:recv_bytes])
     bad = np.flatnonzero(got != want)
     assert bad.size == 0, f"{bad.size} bytes differ, first at {bad[:8]}"
     assert np.array_equal(host(d_arena), arena), "the arena is read only"
     return got
 
 
-def back_to_back(lengths, start=0):
-    p = np.asarray(lengths, np.int64) - 32
-    return (start + np.concatenate([[0], np.cumsum(p)[:-1]])).astype(np.uint64), int(start + p.sum())
+def run(ctx, case, **kw):
+    """check() on a deliver_cases.Case."""
+    return check(ctx, case.arena, case.offsets, case.lengths, case.dst, case.recv_bytes, fixed=case.fixed,
+                 recv_alloc=case.recv_alloc, **kw)
 
 
 def test_golden_receive_plan_deliver(ctx):
@@ -91,79 +101,28 @@ def test_golden_receive_plan_deliver(ctx):
         assert np.array_equal(host(d_wire), wire)
 
 
-PAYLOADS = (2, 4, 14, 16, 18, 30, 32, 34, 62, 64, 66, 126, 130, 1022, 1024, 1026, 1460)
-
-
 @pytest.mark.parametrize("base_mis", [0, 2])
 @pytest.mark.parametrize("src_mod", range(0, 16, 2))
 def test_alignment_matrix(ctx, src_mod, base_mis):
     """Payload start mod 16 (src_mod) x destination mod 16 (all 8) x the payload sizes around every
-    chunk boundary; gaps of 18-48 B between destinations keep their sentinel."""
-    rng = np.random.default_rng(100 + src_mod + base_mis)
-    offsets, lengths, dst = [], [], []
-    at_s, at_d = 0, 0
-    for dst_mod in range(0, 16, 2):
-        for p in PAYLOADS:
-            # the payload (image + 32) at src_mod mod 16 of the allocation
-            at_s = (at_s + 15) // 16 * 16 + (src_mod - 32 - base_mis) % 16
-            offsets.append(at_s)
-            lengths.append(32 + p)
-            at_s += 32 + p + 2 * int(rng.integers(0, 9))
-            at_d = (at_d + 18 + 15) // 16 * 16 + dst_mod
-            dst.append(at_d)
-            at_d += p
-    arena = rng.integers(0, 256, at_s + 16, dtype=np.uint8)
-    order = rng.permutation(len(dst))  # images in any order of destination
-    offsets, lengths, dst = (np.asarray(v)[order] for v in (offsets, lengths, dst))
-    if base_mis == 0:
-        check(ctx, arena, offsets, lengths, dst, at_d + 32)
-        return
-    # the same with the arena itself at 2 mod 16
-    buf = torch.zeros(arena.size + 16, dtype=torch.uint8, device="cuda")
-    buf[base_mis:base_mis + arena.size] = dev(arena)
-    d_recv = torch.full((at_d + 32,), FILL, dtype=torch.uint8, device="cuda")
-    ctx.batch_deliver(buf.data_ptr() + base_mis, len(dst), dev(dst.astype(np.uint64)), d_recv, at_d + 32,
-                      offsets=dev(offsets.astype(np.uint64)), lengths=dev(lengths.astype(np.uint32)))
-    want = deliver_np(arena, offsets, lengths, dst, np.full(at_d + 32, FILL, np.uint8))
-    assert np.array_equal(host(d_recv), want)
+    chunk boundary; gaps of 18-48 B between destinations keep their sentinel.  base_mis 2: the same
+    with the arena itself at 2 mod 16."""
+    run(ctx, alignment_case(src_mod, base_mis), base_mis=base_mis)
 
 
 @pytest.mark.parametrize("count", [1, 63, 64, 65, 257])
 @pytest.mark.parametrize("layout", ["fixed", "slots", "packed"])
 def test_shapes(ctx, count, layout):
-    rng = np.random.default_rng(count)
-    if layout == "fixed":
-        length, stride = 1492, 1500
-        lengths = np.full(count, length)
-        offsets = np.arange(count) * stride
-    elif layout == "slots":  # the C3 mix in 2048-B receive slots
-        lengths = np.asarray((96, 608, 1492))[rng.integers(0, 3, count)]
-        offsets = np.arange(count) * 2048
-    else:
-        lengths = 32 + 2 * rng.integers(0, 400, count)
-        offsets = np.concatenate([[0], np.cumsum(lengths)[:-1]])
-    arena = rng.integers(0, 256, int(offsets[-1] + lengths[-1]), dtype=np.uint8)
-    dst, total = back_to_back(lengths, start=2 * count % 16)
-    check(ctx, arena, offsets, lengths, dst, total + 6, fixed=(stride, length) if layout == "fixed" else None)
-    # every third image skipped: the others keep their places, the holes their sentinel
-    holes = dst.copy()
-    holes[::3] = SKIP
-    check(ctx, arena, offsets, lengths, holes, total + 6, fixed=(stride, length) if layout == "fixed" else None)
+    # back to back, then every third image skipped: the others keep their places, the holes their sentinel
+    for c in shapes_cases(count, layout):
+        run(ctx, c)
 
 
 @pytest.mark.parametrize("length,count", [(9000, 7), (65536, 5), (65536, 1)])
 def test_jumbo(ctx, length, count):
-    rng = np.random.default_rng(length + count)
-    stride = length + 16
-    arena = rng.integers(0, 256, stride * count, dtype=np.uint8)
-    lengths = np.full(count, length)
-    dst, total = back_to_back(lengths, start=10)
-    check(ctx, arena, np.arange(count) * stride, lengths, dst, total + 2, fixed=(stride, length))
-    lengths[-1] = 32 + 2  # a list with one tiny image among the jumbo ones, 2-B aligned images
-    offsets = (np.arange(count) * stride + 2 * np.arange(count))[::-1]  # in descending order of address
-    lengths = lengths[::-1]
-    dst, total = back_to_back(lengths, start=4)
-    check(ctx, arena, offsets, lengths, dst, total)
+    # fixed stride, then a list with one tiny image among the jumbo ones, in descending order of address
+    for c in jumbo_cases(length, count):
+        run(ctx, c)
 
 
 def test_all_skip_empty_and_zero_payload(ctx):
@@ -186,39 +145,20 @@ def test_all_skip_empty_and_zero_payload(ctx):
 
 def test_scattered_destinations(ctx):
     """Destinations in shuffled order with gaps of every even size; the gaps keep their sentinel."""
-    rng = np.random.default_rng(17)
-    n = 1500
-    lengths = 32 + 2 * rng.integers(0, 120, n)
-    lengths[rng.integers(0, n, 20)] = 1492
-    offsets = np.arange(n) * 1536 + 2 * rng.integers(0, 8, n)
-    arena = rng.integers(0, 256, n * 1536 + 16, dtype=np.uint8)
-    gaps = 2 * rng.integers(0, 40, n)
-    order = rng.permutation(n)
-    dst = np.empty(n, np.int64)
-    at = 0
-    for k in order:
-        at += int(gaps[k])
-        dst[k] = at
-        at += int(lengths[k]) - 32
-    check(ctx, arena, offsets, lengths, dst.astype(np.uint64), at + 10)
+    run(ctx, scattered_case())
 
 
 def test_guard_rails(ctx):
     """A range that ends exactly at recv_bytes is delivered; one that ends 2 B past it, an odd dst and
     a dst far outside are skipped whole; the bytes after recv_bytes and the neighbours are intact."""
-    rng = np.random.default_rng(23)
-    n, recv_bytes = 12, 4096
-    lengths = np.full(n, 32 + 100)
-    offsets = np.arange(n) * 256
-    arena = rng.integers(0, 256, n * 256, dtype=np.uint8)
-    dst = np.asarray([0, 100, 201, 300, recv_bytes - 100, recv_bytes - 98, recv_bytes, recv_bytes + 2, 1 << 40,
-                      (1 << 64) - 2, 3800, 500], np.uint64)
-    got = check(ctx, arena, offsets, lengths, dst, recv_bytes, recv_alloc=recv_bytes + 256)
+    first, odd, zero = guard_rails_cases()
+    got = run(ctx, first)
+    recv_bytes, arena = first.recv_bytes, first.arena
     assert np.array_equal(got[recv_bytes - 100:recv_bytes], arena[4 * 256 + 32:4 * 256 + 132])
     assert (got[recv_bytes:] == FILL).all() and (got[200:300] == FILL).all()
     # recv_bytes itself odd or tiny
-    check(ctx, arena, offsets[:3], lengths[:3], [0, 100, 200], 299, recv_alloc=512)
-    check(ctx, arena, offsets[:3], lengths[:3], [0, 100, 200], 0, recv_alloc=512)
+    run(ctx, odd)
+    run(ctx, zero)
 
 
 def test_past_4gib(ctx):
