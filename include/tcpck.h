@@ -266,6 +266,130 @@ int tcpck_plan_deliver(const void *h_hdr, const uint8_t *h_ok, const uint32_t *h
                        uint64_t count, tcpck_rcv_state *st, uint64_t recv_bytes,
                        uint64_t *h_dst, uint8_t *h_verdict, uint32_t *h_ack, uint64_t *consumed);
 
+/* ---- receive demultiplex: which connection an image belongs to -------------
+ * A receive ring holds datagrams of many connections.  The reference, per
+ * packet, between TcpHeaderN2H and RecvPacket: SocketManager::ReceivePacket
+ * (include/socket-manager.h:181-208) finds the socket in identifier_to_socket_
+ * (FindInternal, :235-245), an unordered_map find under the manager's mutex:
+ *   key       host_port = DestinationPort(), peer_ip = SourceAddress(),
+ *             peer_port = SourcePort(); the host address is the manager's own
+ *             ip_ -- the packet's DestinationAddress() is NOT looked at, so a
+ *             datagram addressed elsewhere still finds the socket (:187-196);
+ *   listener  Syn() && !Ack() looks up (host_port, 0, 0); everything else --
+ *             SYN+ACK and a packet with neither flag included -- the full key;
+ *   equality  exact on all fields (include/socket-internal.h:65-69);
+ *   checksum  the lookup does not depend on the verdict; a found socket gets
+ *             RecvPacket(packet, ok); not found and ok: a RST whose sequence
+ *             number is the packet's acknowledgement number (RstHeader,
+ *             socket-internal.h:43-50); not found and !ok: nothing.
+ *
+ * The connection table: the map's keys with a caller-chosen u32 id each, a
+ * host mirror (set / erase / find) and a device image (commit) the demux kernel
+ * probes.  Open addressing, linear probing, 16-B slots, a power-of-two slot
+ * count >= 2 * max_conns (at least 64), so an empty slot always ends a probe;
+ * the image is rebuilt from the entries at every commit (no tombstones).  The
+ * reference's hash is not observable; the one here is the library's own.
+ * Listeners are ordinary entries with peer_ip = 0, peer_port = 0.
+ *   create   max_conns in [1, 2^22].  ctx != NULL: the image's device memory is
+ *            allocated here, once, on the context's device (the context must
+ *            outlive the table's last use).  ctx == NULL: a host-only table --
+ *            set / erase / find / commit / stats work (commit rebuilds the host
+ *            image and uploads nothing), tcpck_batch_demux refuses it.
+ *   set      adds the key or overwrites its id (identifier_to_socket_[key] =
+ *            ..., socket-manager.h:70-90).  id == TCPCK_CONN_NONE:
+ *            TCPCK_EINVAL.  A new key beyond max_conns: TCPCK_ENOMEM, the
+ *            table as it was.
+ *   erase    an absent key is TCPCK_OK (unordered_map::erase).
+ *   find     reads the host mirror (committed or not): *id = the key's id or
+ *            TCPCK_CONN_NONE.
+ *   commit   rebuilds the image from the mirror's entries and uploads it on
+ *            `stream`.  Control plane: it blocks until the upload is done.
+ *            Demux launches enqueued on that stream after it returns see
+ *            exactly the committed entries, launches enqueued there earlier
+ *            the previous commit; ordering against other streams is the
+ *            caller's.
+ *   stats    of the image as last committed (all 0 before the first commit):
+ *            *slots, *entries, *longest_probe = the most slots a lookup
+ *            inspects to find an entry, *wrapped = the entries whose probe run
+ *            passes the end of the slot array.  Any out-pointer may be NULL.
+ * TCPCK_EINVAL: a NULL table or (create, find) out-pointer, max_conns out of
+ * range.  Not thread-safe: calls on one table are the caller's to serialise
+ * (the reference runs them under the manager's mutex). */
+#define TCPCK_CONN_NONE UINT32_MAX
+typedef struct tcpck_conn_table tcpck_conn_table;
+int tcpck_conn_table_create(tcpck_ctx *ctx, uint32_t max_conns, tcpck_conn_table **out);
+int tcpck_conn_table_destroy(tcpck_conn_table *t);
+int tcpck_conn_table_set(tcpck_conn_table *t, uint16_t host_port, uint32_t peer_ip, uint16_t peer_port, uint32_t id);
+int tcpck_conn_table_erase(tcpck_conn_table *t, uint16_t host_port, uint32_t peer_ip, uint16_t peer_port);
+int tcpck_conn_table_find(const tcpck_conn_table *t, uint16_t host_port, uint32_t peer_ip, uint16_t peer_port, uint32_t *id);
+int tcpck_conn_table_commit(tcpck_conn_table *t, tcpck_stream stream);
+int tcpck_conn_table_stats(const tcpck_conn_table *t, uint64_t *slots, uint64_t *entries, uint32_t *longest_probe, uint64_t *wrapped);
+
+/* The batched lookup.  d_hdr: the dense host-order header array of
+ * tcpck_batch_receive (d_hdr != NULL there), 32 * count bytes, 4-B aligned:
+ * the source address is the u32 at byte 0, the source and destination ports
+ * the u16 at bytes 12 and 14, the flags byte 25 (ACK 0x08, SYN 0x40).
+ * d_conn[k] (u32, 4-B aligned) = the id the committed table holds for image
+ * k's key under the rules above, else TCPCK_CONN_NONE.  d_hdr is only read;
+ * nothing past d_conn[count) is written.  Asynchronous on `stream`; nothing is
+ * allocated; no host synchronisation.  count == 0 is TCPCK_OK.  TCPCK_EINVAL:
+ * ctx or t NULL; a host-only table, a table of another device or one never
+ * committed; with count > 0 a NULL or misaligned d_hdr or d_conn. */
+int tcpck_batch_demux(tcpck_ctx *ctx, const tcpck_conn_table *t, const void *d_hdr, uint64_t count,
+                      uint32_t *d_conn, tcpck_stream stream);
+
+/* The host planner over a mixed ring: tcpck_plan_deliver for every connection
+ * of the ring at once, in ring order.  h_hdr, h_ok, h_lengths / len as in
+ * tcpck_plan_deliver; h_conn[k]: image k's connection, TCPCK_CONN_NONE or an
+ * index into conns[0, n_conns) (the ids of the connection table are these
+ * indices).  conns[c].rcv is the connection's control block, conns[c].recv_base
+ * / recv_bytes its window of one shared receive buffer (rcv.delivered counts
+ * within the window); disjoint windows are the caller's precondition.
+ * Every conns[c].stopped_at is set to TCPCK_NOT_STOPPED on entry.  Image k, c
+ * = h_conn[k]:
+ *   c == NONE       no socket (socket-manager.h:197-207): h_dst[k] = SKIP; bad
+ *                   sum: verdict 0, h_ack[k] = 0; good sum: TCPCK_RCV_RST,
+ *                   h_ack[k] = the image's acknowledgement number (header
+ *                   bytes 20-23), the RST's sequence number -- but once an
+ *                   earlier image of this call got TCPCK_RCV_HOST, a good-sum
+ *                   unknown image gets TCPCK_RCV_HOST (h_ack[k] = 0): a SYN
+ *                   handed to a listener makes the reference insert a new
+ *                   socket (InternalNewConnection, socket-manager.h:70-90)
+ *                   that later packets of that peer find and the committed
+ *                   table cannot know, so the host looks those up again;
+ *   CONN_HOST set   TCPCK_RCV_HOST, SKIP, h_ack[k] = conns[c].rcv.rcv_nxt, no
+ *                   state change: listeners, handshakes, closing connections;
+ *   c stopped       verdict 0, SKIP, h_ack[k] = rcv_nxt (what
+ *                   tcpck_plan_deliver writes from `consumed` on);
+ *   otherwise       exactly one step of tcpck_plan_deliver on conns[c].rcv
+ *                   against conns[c].recv_bytes (the same code); an appended
+ *                   payload gets h_dst[k] = recv_base + rcv.delivered,
+ *                   absolute in the shared buffer.  Where the single planner
+ *                   would stop (a FIN in sequence, a payload that does not
+ *                   fit) only this connection stops: stopped_at = k, verdict
+ *                   0, SKIP, h_ack[k] = rcv_nxt; the others go on.
+ * The result feeds tcpck_batch_deliver unchanged: one launch over the ring,
+ * d_recv the shared buffer, recv_bytes its whole size.  TCPCK_EINVAL, nothing
+ * written: with count > 0 a NULL h_hdr, h_ok, h_conn, h_dst, h_verdict or
+ * h_ack; n_conns > 0 and conns NULL; a bad length (as tcpck_plan_deliver); an
+ * h_conn[k] neither TCPCK_CONN_NONE nor < n_conns; an odd recv_base;
+ * recv_base + recv_bytes overflowing; rcv.delivered > recv_bytes. */
+#define TCPCK_CONN_ESTAB 0u       /* planned here by Estab's rule */
+#define TCPCK_CONN_HOST 1u        /* listener, handshake, closing: every image goes to the host state machine */
+#define TCPCK_NOT_STOPPED UINT64_MAX
+#define TCPCK_RCV_RST 16u         /* no socket, good sum: reply RST, seq = h_ack[k] (the image's ack number) */
+#define TCPCK_RCV_HOST 32u        /* not decided here: run this image through the host path, in arrival order */
+typedef struct tcpck_conn_state {
+  tcpck_rcv_state rcv;            /* as tcpck_plan_deliver; rcv.delivered counts within this window */
+  uint64_t recv_base, recv_bytes; /* this connection's window of the shared receive buffer; recv_base even */
+  uint64_t stopped_at;            /* out: TCPCK_NOT_STOPPED, or the ring index where this connection's walk stopped */
+  uint32_t flags, reserved;
+} tcpck_conn_state;
+int tcpck_plan_deliver_multi(const void *h_hdr, const uint8_t *h_ok, const uint32_t *h_conn,
+                             const uint32_t *h_lengths, uint32_t len, uint64_t count,
+                             tcpck_conn_state *conns, uint32_t n_conns,
+                             uint64_t *h_dst, uint8_t *h_verdict, uint32_t *h_ack);
+
 /* ---- batched segmentation: send stream -> checksummed images -------------
  * The data-segment send path in one device pass.  The reference, per segment:
  * TcpSendingBuffer::GetAsTcpPacket(0, window) cuts the next <= window bytes

@@ -58,6 +58,14 @@ RCV_PAYLOAD = 2   # ... and Accept() appends its payload (dst[k] set)
 RCV_SEND_ACK = 4  # the reference replies SendAck(snd_nxt, ack[k], .)
 RCV_BAD_SUM = 8   # checksum failed: InvalideCheckSum(), Discard + SendAck
 
+# receive demultiplex (tcpck_conn_table_* / tcpck_batch_demux / tcpck_plan_deliver_multi)
+CONN_NONE = 0xFFFFFFFF  # no entry for the image's key
+CONN_ESTAB = 0    # ConnState.flags: planned by Estab's rule
+CONN_HOST = 1     # ... every image goes to the host state machine
+NOT_STOPPED = 0xFFFFFFFFFFFFFFFF  # ConnState.stopped_at: the connection's walk ran to the end of the ring
+RCV_RST = 16      # no socket, good sum: reply RST, seq = ack[k] (the image's ack number)
+RCV_HOST = 32     # not decided here: the host path takes the image, in arrival order
+
 # include/tcpck_tuning.h
 KERNEL_AUTO = 0
 KERNEL_SEG = 1    # param: seg shape + 1 (1..11, SEG_SHAPES), 0 = by length
@@ -130,6 +138,9 @@ EXPORTS = (
     "tcpck_synth_fixed", "tcpck_synth_var", "tcpck_batch_segment", "tcpck_batch_header_swap",
     "tcpck_batch_receive", "tcpck_host_batch_fixed_multi", "tcpck_host_batch_var_multi",
     "tcpck_batch_deliver", "tcpck_plan_deliver",
+    "tcpck_conn_table_create", "tcpck_conn_table_destroy", "tcpck_conn_table_set", "tcpck_conn_table_erase",
+    "tcpck_conn_table_find", "tcpck_conn_table_commit", "tcpck_conn_table_stats", "tcpck_batch_demux",
+    "tcpck_plan_deliver_multi",
 )
 
 
@@ -150,6 +161,14 @@ class RcvState(ctypes.Structure):
     bytes appended to the receive stream so far."""
     _fields_ = [("rcv_nxt", ctypes.c_uint32), ("snd_nxt", ctypes.c_uint32), ("snd_una", ctypes.c_uint32),
                 ("rcv_wnd", ctypes.c_uint16), ("reserved", ctypes.c_uint16), ("delivered", ctypes.c_uint64)]
+
+
+class ConnState(ctypes.Structure):
+    """tcpck_conn_state: one connection of a mixed ring for plan_deliver_multi -- its control
+    block, its window [recv_base, recv_base + recv_bytes) of the shared receive buffer, where
+    its walk stopped (out) and CONN_ESTAB / CONN_HOST."""
+    _fields_ = [("rcv", RcvState), ("recv_base", ctypes.c_uint64), ("recv_bytes", ctypes.c_uint64),
+                ("stopped_at", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 _libs: dict = {}
@@ -201,6 +220,16 @@ def lib(probe: bool = False) -> ctypes.CDLL:
         "tcpck_batch_deliver": (i32, [vp, vp, u64, u32, vp, vp, u64, vp, vp, u64, vp]),
         "tcpck_plan_deliver": (i32, [vp, vp, vp, u32, u64, ctypes.POINTER(RcvState), u64, vp, vp, vp,
                                      ctypes.POINTER(u64)]),
+        "tcpck_conn_table_create": (i32, [vp, u32, ctypes.POINTER(vp)]),
+        "tcpck_conn_table_destroy": (i32, [vp]),
+        "tcpck_conn_table_set": (i32, [vp, ctypes.c_uint16, u32, ctypes.c_uint16, u32]),
+        "tcpck_conn_table_erase": (i32, [vp, ctypes.c_uint16, u32, ctypes.c_uint16]),
+        "tcpck_conn_table_find": (i32, [vp, ctypes.c_uint16, u32, ctypes.c_uint16, ctypes.POINTER(u32)]),
+        "tcpck_conn_table_commit": (i32, [vp, vp]),
+        "tcpck_conn_table_stats": (i32, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u32),
+                                         ctypes.POINTER(u64)]),
+        "tcpck_batch_demux": (i32, [vp, vp, vp, u64, vp, vp]),
+        "tcpck_plan_deliver_multi": (i32, [vp, vp, vp, vp, u32, u64, ctypes.POINTER(ConnState), u32, vp, vp, vp]),
         # include/tcpck_tuning.h
         "tcpck_batch_fixed_ex": (i32, [vp, i32, i32, vp, u64, u32, u64, vp, i32, i32, vp]),
         "tcpck_batch_var_ex": (i32, [vp, i32, i32, vp, vp, vp, u64, vp, ctypes.POINTER(Layout), i32, i32, vp]),
@@ -329,6 +358,92 @@ def plan_deliver(hdr, ok, state: RcvState, recv_bytes: int, lengths=None, length
     return dst, verdict, ack, consumed.value
 
 
+def plan_deliver_multi(hdr, ok, conn, conns, lengths=None, length: int = 0):
+    """tcpck_plan_deliver_multi on numpy arrays (host only): plan_deliver over a ring that mixes
+    connections.  conn = batch_demux's ids (CONN_NONE or an index into conns), conns = a ctypes
+    array (ConnState * n) or a list of ConnState, updated in place (rcv, stopped_at).  Returns
+    (dst u64[n], verdict u8[n], ack u32[n]): dst is absolute in the shared receive buffer and feeds
+    one batch_deliver over the whole ring."""
+    import numpy as np
+    ok = np.ascontiguousarray(ok, dtype=np.uint8)
+    n = ok.size
+    hdr = np.ascontiguousarray(hdr, dtype=np.uint8).reshape(-1)
+    conn = np.ascontiguousarray(conn, dtype=np.uint32)
+    if hdr.size != 32 * n or conn.size != n:
+        raise ValueError("hdr must hold 32 bytes and conn one entry per image")
+    if lengths is not None:
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        if lengths.size != n:
+            raise ValueError("lengths must hold one entry per image")
+    arr = conns if isinstance(conns, ctypes.Array) else (ConnState * len(conns))(*conns)
+    dst = np.empty(n, np.uint64)
+    verdict = np.empty(n, np.uint8)
+    ack = np.empty(n, np.uint32)
+    status = lib().tcpck_plan_deliver_multi(hdr.ctypes.data, ok.ctypes.data, conn.ctypes.data, _ptr(lengths), length, n,
+                                            arr, len(arr), dst.ctypes.data, verdict.ctypes.data, ack.ctypes.data)
+    _check(status, "tcpck_plan_deliver_multi")
+    if arr is not conns:  # a list: its elements were copied into the array
+        for i, c in enumerate(conns):
+            ctypes.memmove(ctypes.byref(c), ctypes.byref(arr[i]), ctypes.sizeof(ConnState))
+    return dst, verdict, ack
+
+
+class ConnTable:
+    """tcpck_conn_table: ReceivePacket's socket map (socket-manager.h:187-196, 235-245) as a host
+    mirror plus a device image batch_demux probes.  Keys are (host_port, peer_ip, peer_port), a
+    listener is (host_port, 0, 0); ids are the caller's (for plan_deliver_multi: indices into its
+    conns).  ctx None: a host-only table (no device; batch_demux refuses it)."""
+
+    def __init__(self, ctx, max_conns: int):
+        self._L = ctx._L if ctx is not None else lib()
+        self._h = ctypes.c_void_p()
+        _check(self._L.tcpck_conn_table_create(ctx._h if ctx is not None else None, max_conns, ctypes.byref(self._h)),
+               "tcpck_conn_table_create")
+        self._ctx = ctx  # the context outlives the table
+        self.max_conns = max_conns
+
+    def set(self, host_port: int, peer_ip: int, peer_port: int, id: int) -> None:
+        _check(self._L.tcpck_conn_table_set(self._h, host_port, peer_ip, peer_port, id), "tcpck_conn_table_set")
+
+    def erase(self, host_port: int, peer_ip: int, peer_port: int) -> None:
+        _check(self._L.tcpck_conn_table_erase(self._h, host_port, peer_ip, peer_port), "tcpck_conn_table_erase")
+
+    def find(self, host_port: int, peer_ip: int, peer_port: int) -> int:
+        """The key's id in the host mirror, or CONN_NONE."""
+        out = ctypes.c_uint32()
+        _check(self._L.tcpck_conn_table_find(self._h, host_port, peer_ip, peer_port, ctypes.byref(out)),
+               "tcpck_conn_table_find")
+        return out.value
+
+    def commit(self, stream=None) -> None:
+        """Rebuilds the image from the mirror and uploads it on `stream` (blocks until done)."""
+        _check(self._L.tcpck_conn_table_commit(self._h, _stream(stream)), "tcpck_conn_table_commit")
+
+    def stats(self):
+        """(slots, entries, longest_probe, wrapped) of the image as last committed."""
+        s, e, w, p = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+        _check(self._L.tcpck_conn_table_stats(self._h, ctypes.byref(s), ctypes.byref(e), ctypes.byref(p),
+                                              ctypes.byref(w)), "tcpck_conn_table_stats")
+        return s.value, e.value, p.value, w.value
+
+    def close(self) -> None:
+        if self._h:
+            self._L.tcpck_conn_table_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---- context -------------------------------------------------------------------
 
 class Context:
@@ -416,6 +531,14 @@ class Context:
         DELIVER_SKIP; every other byte of recv keeps its value.  Layout as batch_receive."""
         _check(self._L.tcpck_batch_deliver(self._h, _ptr(arena), stride, length, _ptr(offsets), _ptr(lengths), count,
                                            _ptr(dst), _ptr(recv), recv_bytes, _stream(stream)), "tcpck_batch_deliver")
+
+    def batch_demux(self, table: "ConnTable", hdr, count: int, conn, stream=None) -> None:
+        """ReceivePacket's socket lookup for a batch (tcpck_batch_demux, socket-manager.h:187-196):
+        conn[k] (u32) = the id `table`, as last committed, holds for image k's key -- (dst port, src
+        address, src port), or (dst port, 0, 0) for a SYN without ACK -- else CONN_NONE.  hdr: the
+        dense host-order header array batch_receive writes."""
+        _check(self._L.tcpck_batch_demux(self._h, table._h if table is not None else None, _ptr(hdr), count,
+                                         _ptr(conn), _stream(stream)), "tcpck_batch_demux")
 
     def batch_segment(self, payload, payload_bytes: int, seg: int, hdr, seq0: int, images, stride: int,
                       out=None, mode: int = MODE_REF, param: int | None = None, stream=None) -> int:
