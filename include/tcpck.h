@@ -390,6 +390,74 @@ int tcpck_plan_deliver_multi(const void *h_hdr, const uint8_t *h_ok, const uint3
                              tcpck_conn_state *conns, uint32_t n_conns,
                              uint64_t *h_dst, uint8_t *h_verdict, uint32_t *h_ack);
 
+/* ---- batched replies: the planners' verdicts -> the ACK / RST ring ---------
+ * What the reference sends back for a received datagram, for a whole ring:
+ *   ACK  SocketInternal::SendAck (include/socket-internal.h:293-299):
+ *        MakeTcpPacket(0), AckHeader(seq, ack, wnd) sets the ACK bit, seq, ack
+ *        and window; SocketInternal::SendPacket (src/socket-internal.cc:35-42)
+ *        SetSource / SetDestination and TcpHeaderH2N; SocketManager::SendPacket
+ *        (src/socket-manager.cc:6-12) Checksum() = 0, then the checksum.  The
+ *        call sites are Estab's data branch (src/state.cc:203-210) and
+ *        InvalideCheckSum (include/state.h:268-275): seq = snd_nxt, wnd =
+ *        snd_wnd in both;
+ *   RST  for a datagram of no socket (ReceivePacket,
+ *        include/socket-manager.h:201-207): MakeTcpPacket(0), RstHeader sets
+ *        the RST bit and seq = the packet's acknowledgement number,
+ *        TcpHeaderH2N, the checksum -- and NO SetSource / SetDestination: this
+ *        RST leaves with zero addresses and ports, which is kept.
+ * The reference's packet constructor leaves every byte the helpers do not set
+ * (8-11, 24, the other bits of 25, 30-31) as the heap held it; here an ACK
+ * takes them from the connection's template and an RST has them zero.
+ *
+ * d_verdict[k], d_ack[k]: the planner's h_verdict / h_ack (tcpck_plan_deliver,
+ * tcpck_plan_deliver_multi), uploaded by the caller.  d_conn[k]: image k's
+ * connection (tcpck_batch_demux's ids); NULL: every image is connection 0.
+ * d_tmpl: one 32-B network-order header per connection, 32 * n_conns bytes --
+ * the same kind of header tcpck_batch_segment takes as `hdr`, with bytes 16-19
+ * = htonl(snd_nxt) and 26-27 = htons(snd_wnd); keeping snd_nxt current there
+ * is the caller's (4 bytes per connection that sent).  Per image k, c =
+ * d_conn ? d_conn[k] : 0:
+ *   verdict & TCPCK_RCV_RST           32 zero bytes, bytes 16-19 :=
+ *                                     htonl(d_ack[k]), byte 25 := 0x20; c is
+ *                                     not looked at;
+ *   else verdict & TCPCK_RCV_SEND_ACK and c < n_conns
+ *                                     template c, bytes 20-23 :=
+ *                                     htonl(d_ack[k]), byte 25 |= 0x08;
+ *   else                              no reply (TCPCK_RCV_HOST, verdict 0,
+ *                                     SEND_ACK with c == TCPCK_CONN_NONE or c
+ *                                     >= n_conns: no template is read outside
+ *                                     [0, n_conns), whatever the arrays hold).
+ * Bytes 28-29 of every reply end as tcpck_fill16(image, 32, mode) leaves them
+ * (both modes).  Reply j goes to d_replies + 32 j: dense and in ring order, the
+ * j-th reply answers the j-th replying image (the reference replies in arrival
+ * order); d_src[j] = k (d_src may be NULL); *d_count (device, u64) = the number
+ * of replying images.  When that exceeds reply_cap only the first reply_cap
+ * replies and d_src entries are written and *d_count still holds the total.
+ * Nothing is written past d_replies[32 * min(total, reply_cap)) or
+ * d_src[min(total, reply_cap)); the inputs are only read.  d_scratch: device
+ * memory of the size tcpck_reply_scratch_bytes(count, &bytes) gives (never 0),
+ * its contents undefined before and after.  Asynchronous on `stream`; nothing
+ * is allocated; no host synchronisation; the same inputs give the same bytes.
+ * count == 0 is TCPCK_OK and sets *d_count = 0 in stream order when d_count is
+ * not NULL.  TCPCK_EINVAL, nothing launched: ctx NULL; a bad mode; count >
+ * 2^31; with count > 0 a NULL d_verdict, d_ack, d_replies, d_count or
+ * d_scratch; n_conns > 0 with d_tmpl NULL; a misaligned pointer (d_ack, d_conn,
+ * d_src 4-B; d_tmpl, d_replies, d_scratch 16-B; d_count 8-B).
+ * tcpck_reply_scratch_bytes: TCPCK_EINVAL for bytes NULL or count > 2^31. */
+#define TCPCK_REPLY_BYTES 32
+int tcpck_reply_scratch_bytes(uint64_t count, size_t *bytes);
+int tcpck_batch_reply(tcpck_ctx *ctx, int mode, const uint8_t *d_verdict, const uint32_t *d_ack,
+                      const uint32_t *d_conn, const void *d_tmpl, uint32_t n_conns, uint64_t count,
+                      void *d_replies, uint64_t reply_cap, uint32_t *d_src, uint64_t *d_count,
+                      void *d_scratch, tcpck_stream stream);
+/* The same contract on host arrays: plain host C++, reentrant, no device, no
+ * scratch; the number of replying images is returned through n_replies.  The
+ * CPU fallback and the second implementation the device call is tested
+ * against.  Nothing is written on an error. */
+int tcpck_build_replies(int mode, const uint8_t *h_verdict, const uint32_t *h_ack, const uint32_t *h_conn,
+                        const void *h_tmpl, uint32_t n_conns, uint64_t count,
+                        void *h_replies, uint64_t reply_cap, uint32_t *h_src, uint64_t *n_replies);
+
 /* ---- batched segmentation: send stream -> checksummed images -------------
  * The data-segment send path in one device pass.  The reference, per segment:
  * TcpSendingBuffer::GetAsTcpPacket(0, window) cuts the next <= window bytes

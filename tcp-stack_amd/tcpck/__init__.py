@@ -65,6 +65,7 @@ CONN_HOST = 1     # ... every image goes to the host state machine
 NOT_STOPPED = 0xFFFFFFFFFFFFFFFF  # ConnState.stopped_at: the connection's walk ran to the end of the ring
 RCV_RST = 16      # no socket, good sum: reply RST, seq = ack[k] (the image's ack number)
 RCV_HOST = 32     # not decided here: the host path takes the image, in arrival order
+REPLY_BYTES = 32  # one reply of tcpck_batch_reply / tcpck_build_replies: a header, no payload
 
 # include/tcpck_tuning.h
 KERNEL_AUTO = 0
@@ -141,6 +142,7 @@ EXPORTS = (
     "tcpck_conn_table_create", "tcpck_conn_table_destroy", "tcpck_conn_table_set", "tcpck_conn_table_erase",
     "tcpck_conn_table_find", "tcpck_conn_table_commit", "tcpck_conn_table_stats", "tcpck_batch_demux",
     "tcpck_plan_deliver_multi",
+    "tcpck_reply_scratch_bytes", "tcpck_batch_reply", "tcpck_build_replies",
 )
 
 
@@ -230,6 +232,9 @@ def lib(probe: bool = False) -> ctypes.CDLL:
                                          ctypes.POINTER(u64)]),
         "tcpck_batch_demux": (i32, [vp, vp, vp, u64, vp, vp]),
         "tcpck_plan_deliver_multi": (i32, [vp, vp, vp, vp, u32, u64, ctypes.POINTER(ConnState), u32, vp, vp, vp]),
+        "tcpck_reply_scratch_bytes": (i32, [u64, ctypes.POINTER(sz)]),
+        "tcpck_batch_reply": (i32, [vp, i32, vp, vp, vp, vp, u32, u64, vp, u64, vp, vp, vp, vp]),
+        "tcpck_build_replies": (i32, [i32, vp, vp, vp, vp, u32, u64, vp, u64, vp, ctypes.POINTER(u64)]),
         # include/tcpck_tuning.h
         "tcpck_batch_fixed_ex": (i32, [vp, i32, i32, vp, u64, u32, u64, vp, i32, i32, vp]),
         "tcpck_batch_var_ex": (i32, [vp, i32, i32, vp, vp, vp, u64, vp, ctypes.POINTER(Layout), i32, i32, vp]),
@@ -388,6 +393,43 @@ def plan_deliver_multi(hdr, ok, conn, conns, lengths=None, length: int = 0):
     return dst, verdict, ack
 
 
+def reply_scratch_bytes(count: int) -> int:
+    """Bytes of device scratch Context.batch_reply needs for a ring of `count` images (never 0)."""
+    out = ctypes.c_size_t()
+    _check(lib().tcpck_reply_scratch_bytes(count, ctypes.byref(out)), "tcpck_reply_scratch_bytes")
+    return out.value
+
+
+def build_replies(verdict, ack, tmpl, conn=None, reply_cap: int | None = None, mode: int = MODE_REF):
+    """tcpck_build_replies on numpy arrays (host only, no device): the ACK / RST datagrams the
+    reference sends back for a planned ring (SendAck, socket-internal.h:293-299; the RST of a datagram
+    of no socket, socket-manager.h:201-207).  verdict / ack: the planner's outputs; conn: the demux
+    ids (None: every image is connection 0); tmpl: 32 B of network-order header per connection (seq =
+    snd_nxt, window = snd_wnd).  Returns (replies u8[written, 32], src u32[written], total): dense, in
+    ring order, src[j] the image reply j answers; written = min(total, reply_cap) (reply_cap None: the
+    image count)."""
+    import numpy as np
+    verdict = np.ascontiguousarray(verdict, dtype=np.uint8)
+    n = verdict.size
+    ack = np.ascontiguousarray(ack, dtype=np.uint32)
+    tmpl = np.ascontiguousarray(tmpl, dtype=np.uint8).reshape(-1)
+    if ack.size != n or tmpl.size % 32:
+        raise ValueError("ack must hold one entry per image and tmpl 32 bytes per connection")
+    if conn is not None:
+        conn = np.ascontiguousarray(conn, dtype=np.uint32)
+        if conn.size != n:
+            raise ValueError("conn must hold one entry per image")
+    cap = n if reply_cap is None else reply_cap
+    replies = np.zeros((cap + 1) * 32, np.uint8)  # (one record more: never an empty array's NULL)
+    src = np.zeros(cap + 1, np.uint32)
+    total = ctypes.c_uint64()
+    _check(lib().tcpck_build_replies(mode, verdict.ctypes.data, ack.ctypes.data, _ptr(conn), tmpl.ctypes.data if tmpl.size
+                                     else None, tmpl.size // 32, n, replies.ctypes.data, cap, src.ctypes.data,
+                                     ctypes.byref(total)), "tcpck_build_replies")
+    written = min(total.value, cap)
+    return replies[:32 * written].reshape(-1, 32), src[:written], total.value
+
+
 class ConnTable:
     """tcpck_conn_table: ReceivePacket's socket map (socket-manager.h:187-196, 235-245) as a host
     mirror plus a device image batch_demux probes.  Keys are (host_port, peer_ip, peer_port), a
@@ -539,6 +581,17 @@ class Context:
         dense host-order header array batch_receive writes."""
         _check(self._L.tcpck_batch_demux(self._h, table._h if table is not None else None, _ptr(hdr), count,
                                          _ptr(conn), _stream(stream)), "tcpck_batch_demux")
+
+    def batch_reply(self, verdict, ack, tmpl, n_conns: int, count: int, replies, reply_cap: int, total, scratch,
+                    conn=None, src=None, mode: int = MODE_REF, stream=None) -> None:
+        """The planners' verdicts -> the dense, checksummed, network-order ACK / RST ring
+        (tcpck_batch_reply): device arrays verdict u8[count], ack u32[count], conn u32[count] or None
+        (every image connection 0), tmpl 32 B per connection; reply j at replies + 32 j for j <
+        reply_cap, src[j] (u32, or None) the image it answers, total (one u64) the number of replying
+        images; scratch: reply_scratch_bytes(count) bytes of device memory."""
+        _check(self._L.tcpck_batch_reply(self._h, mode, _ptr(verdict), _ptr(ack), _ptr(conn), _ptr(tmpl), n_conns, count,
+                                         _ptr(replies), reply_cap, _ptr(src), _ptr(total), _ptr(scratch),
+                                         _stream(stream)), "tcpck_batch_reply")
 
     def batch_segment(self, payload, payload_bytes: int, seg: int, hdr, seq0: int, images, stride: int,
                       out=None, mode: int = MODE_REF, param: int | None = None, stream=None) -> int:
