@@ -256,7 +256,9 @@ int tcpck_batch_deliver(tcpck_ctx *ctx, const void *d_arena, uint64_t stride, ui
 typedef struct tcpck_rcv_state { /* the TcpControlBlock fields Estab reads and writes */
   uint32_t rcv_nxt, snd_nxt, snd_una;
   uint16_t rcv_wnd, reserved;
-  uint64_t delivered;            /* bytes appended to the receive stream so far */
+  uint64_t delivered;            /* bytes appended to the receive stream so far; between calls the
+                                    caller may lower it (to an even value) once it has consumed the
+                                    window's front: the next payload lands at the new value */
 } tcpck_rcv_state;
 #define TCPCK_RCV_ACCEPT 1u   /* Estab's data/ACK branch took the image            */
 #define TCPCK_RCV_PAYLOAD 2u  /* ... and Accept() appends its payload (h_dst[k] set) */
