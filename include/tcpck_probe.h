@@ -76,7 +76,7 @@ int tcpck_probe_scratch_state(tcpck_ctx *ctx, int *allocated, int *used_mask);
  * the allocation 64 out-less FILLs later (not latched). */
 int tcpck_probe_scratch_fail(tcpck_ctx *ctx, int n, uint64_t *refusals);
 
-/* The pipelined FILL (round 6; tcp-stack_amd/csrc/tcpck_api.hip
+/* The pipelined FILL (round 6; tcp-stack_amd/csrc/tcpck_router.hip
  * fill_pipelined) under TCPCK_KERNEL_AUTO in this context: k chunks (0 / 1:
  * the serial form, -1: AUTO's rule), the field pass of chunk i on a context
  * stream of priority prio (hipStreamCreateWithPriority; a changed priority

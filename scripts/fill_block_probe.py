@@ -22,7 +22,7 @@ import torch  # noqa: E402
 import tcpck  # noqa: E402
 import synth_np  # noqa: E402
 
-VV_POLICY = 4 | 8 | 16  # tcpck_api.hip kVvPolicy
+VV_POLICY = 4 | 8 | 16  # tcpck_plan.cc kVvPolicy
 BLK = 128
 MS = []
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Pipelined FILL: the field pass of chunk i on a context
-stream beside the stream pass of chunk i + 1 (tcpck_api.hip fill_pipelined),
+stream beside the stream pass of chunk i + 1 (tcpck_router.hip fill_pipelined),
 against the serial form (stream over all images, then the field pass), at C3
 (4M packed 96/608/1492, the update form) and C2 (1M x 1492 fixed, rstream's
 deferred fields), with and without a results buffer.

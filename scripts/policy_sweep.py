@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Kernel choice vs image size: the data behind run_fixed / run_var's AUTO policy.
+"""Kernel choice vs image size: the data behind the router's AUTO policy (tcpck_plan.cc).
 
 For packed batches of ~1.5 GB with one image length L (fixed stride, and the
 same bytes as a variable layout) and for a few length mixes, times every

@@ -1,6 +1,7 @@
 // tcpck_api_internal.h -- the context and the batch router shared by the C-ABI
-// layer (tcpck_api.hip), its tuning entry points (tcpck_ex.hip in libtcpck.so)
-// and their measurement twins (tcpck_ex_probe.hip in libtcpck_probe.so).  Not
+// layer (tcpck_api.hip, tcpck_host_batch.hip), the router itself
+// (tcpck_router.hip), its tuning entry points (tcpck_ex.hip in libtcpck.so) and
+// their measurement twins (tcpck_ex_probe.hip in libtcpck_probe.so).  Not
 // installed.
 //
 // The router (tcpck::api::batch_*_ex) plans each batch (tcpck_plan.h: the
@@ -108,6 +109,11 @@ constexpr int kProbeParamPatchReverse = 1 << 27;
 
 int hip_status(hipError_t e);
 
+inline bool valid_op_mode(int op, int mode) {
+  return (op == TCPCK_OP_CHECKSUM || op == TCPCK_OP_FILL || op == TCPCK_OP_VERIFY) &&
+         (mode == TCPCK_MODE_REF || mode == TCPCK_MODE_RFC1071);
+}
+
 // Saves the calling thread's current device, switches to `device`, restores.
 class DeviceGuard {
  public:
@@ -121,6 +127,75 @@ class DeviceGuard {
   int prev_ = -1;
   hipError_t ok_ = hipSuccess;
 };
+
+// Where a batch's images are: `count` images of `len` bytes every `stride`
+// bytes from `arena` (the fixed layout: offsets and lengths null, base 0), or
+// image k at arena + offsets[k] - base with lengths[k] bytes (an offset list:
+// stride and len 0), with the caller's layout hint or nullptr.
+struct Images {
+  uint8_t *arena = nullptr;
+  const uint64_t *offsets = nullptr;
+  const uint32_t *lengths = nullptr;
+  uint64_t stride = 0;
+  uint32_t len = 0;
+  uint64_t base = 0;
+  uint64_t count = 0;
+  const tcpck_layout *layout = nullptr;
+  uint64_t total_bytes = 0;  // these images' share of layout->total_bytes (sub)
+  bool lone = false;         // one image cut from a gapped fixed layout (sub): the batch's plan is not its plan
+
+  static Images fixed(uint8_t *arena, uint64_t stride, uint32_t len, uint64_t count) {
+    return {arena, nullptr, nullptr, stride, len, 0, count, nullptr, 0, false};
+  }
+  static Images list(uint8_t *arena, const uint64_t *offsets, const uint32_t *lengths, uint64_t base, uint64_t count,
+                     const tcpck_layout *layout) {
+    return {arena, offsets, lengths, 0, 0, base, count, layout, layout ? layout->total_bytes : 0, false};
+  }
+  bool is_fixed() const { return !offsets; }
+
+  // Images [k0, k0 + n).  An offset list keeps the flags and the length bounds
+  // of its hint, and its byte hint scales with its image count, so its typical
+  // image -- the quantity AUTO chooses by -- is the whole batch's and every
+  // chunk runs the same form (tcpck_tuning.h).  A lone image of a gapped fixed
+  // layout has no stride to speak of: it is one packed image, to be planned
+  // on its own (`lone`).
+  Images sub(uint64_t k0, uint64_t n) const {
+    Images im = *this;
+    im.count = n;
+    if (is_fixed()) {
+      im.arena = arena + k0 * stride;
+      if (n == 1 && stride != len) {
+        im.stride = len;
+        im.lone = true;
+      }
+    } else {
+      im.offsets = offsets + k0;
+      im.lengths = lengths + k0;
+      im.total_bytes = static_cast<uint64_t>(static_cast<unsigned __int128>(total_bytes) * n / count);
+    }
+    return im;
+  }
+};
+
+// The fixed-layout argument checks every entry point shares.
+// (count - 1) * stride + len, the end of the last image, does not fit 64 bits:
+inline bool fixed_end_overflows(uint64_t stride, uint32_t len, uint64_t count) {
+  return count > 1 && stride > (UINT64_MAX - len) / (count - 1);
+}
+// Even `len` and `stride`, images of at least `min_len` bytes that do not
+// overlap, and no overflow.  One image: its stride is never read and becomes
+// `len` (the run kernels assume stride >= len).
+inline bool valid_fixed(uint64_t &stride, uint32_t len, uint64_t count, uint32_t min_len) {
+  if (((len | stride) & 1) || len < min_len || (count > 1 && stride < len) || fixed_end_overflows(stride, len, count))
+    return false;
+  if (count == 1) stride = len;
+  return true;
+}
+// ... for the calls that touch only the first `bytes` of each slot and take no
+// image length: one image's stride may be anything even.
+inline bool valid_fixed_slots(uint64_t stride, uint32_t bytes, uint64_t count) {
+  return count == 1 ? (stride & 1) == 0 : valid_fixed(stride, bytes, count, 0);
+}
 
 // The validated device-batch entry points (tcpck_tuning.h semantics).
 int batch_fixed_ex(tcpck_ctx *ctx, int op, int mode, void *d_arena, uint64_t stride, uint32_t len, uint64_t count,
@@ -138,12 +213,13 @@ int check_receive(const tcpck_ctx *ctx, int mode, const void *d_arena, uint64_t 
                   const void *d_hdr);
 
 // The routed launches behind them (device already selected, arguments valid):
-// plan_fixed / plan_var, then the plan's launches.
-hipError_t run_fixed(tcpck_ctx *ctx, int op, int mode, uint8_t *arena, uint64_t stride, uint32_t len, uint64_t count,
-                     void *out, int kernel, int param, hipStream_t s, uint8_t *hdr, const Hooks &hk);
-hipError_t run_var(tcpck_ctx *ctx, int op, int mode, uint8_t *arena, const uint64_t *off, const uint32_t *len,
-                   uint64_t base, uint64_t count, void *out, const tcpck_layout *layout, int kernel, int param,
-                   hipStream_t s, uint8_t *hdr, const Hooks &hk);
+// the batch's plan (plan_fixed / plan_var), then the plan's launches.
+hipError_t run(tcpck_ctx *ctx, int op, int mode, const Images &im, void *out, int kernel, int param, hipStream_t s,
+               uint8_t *hdr, const Hooks &hk);
+// A FILL from its batch's plan (the FILL front below batch_*_ex's scratch
+// decision; declared for tests/cpp/router_trace.cc).
+hipError_t fill(tcpck_ctx *ctx, const Plan &plan, int mode, const Images &im, uint16_t *out, int kernel, int param,
+                hipStream_t s, const Hooks &hk);
 
 }  // namespace api
 }  // namespace tcpck

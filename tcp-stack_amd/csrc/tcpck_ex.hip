@@ -1,5 +1,6 @@
 // tcpck_ex.hip -- the tuning entry points of libtcpck.so (include/tcpck_tuning.h):
-// the product router with an explicit kernel / param and no measurement hooks.
+// the product router (tcpck_router.hip) with an explicit kernel / param and no
+// measurement hooks.
 // libtcpck_probe.so builds tcpck_ex_probe.hip in this file's place.
 #include <hip/hip_runtime.h>
 

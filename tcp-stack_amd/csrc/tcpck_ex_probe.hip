@@ -2,7 +2,7 @@
 // (include/tcpck_tuning.h) and its measurement-only ones (include/tcpck_probe.h).
 //
 // Built only into the probe library, in place of tcpck_ex.hip: the product
-// router (tcpck::api, tcpck_api.hip) with the measurement hooks switched on,
+// router (tcpck::api, tcpck_router.hip) with the measurement hooks switched on,
 // so that the router itself carries no probe switches.
 //   * tcpck_batch_fixed_ex: also TCPCK_KERNEL_PATCH, FILL's field pass alone,
 //     and RSTREAM 29 / 30, FILL's deferred stream alone (29: the field blocks
@@ -25,6 +25,7 @@
 
 using tcpck::api::DeviceGuard;
 using tcpck::api::Hooks;
+using tcpck::api::Images;
 using tcpck::api::hip_status;
 
 namespace {
@@ -206,10 +207,10 @@ int tcpck_probe_receive_ex(tcpck_ctx *ctx, int mode, void *d_arena, uint64_t str
   if (e == hipSuccess) e = hipStreamWaitEvent(ctx->side, ctx->fork, 0);
   if (e == hipSuccess) e = tcpck::launch_header_swap(h, static_cast<uint32_t>(ctx->num_cus), ctx->side);
   if (e == hipSuccess)
-    e = d_offsets ? tcpck::api::run_var(ctx, TCPCK_OP_VERIFY, mode, arena, d_offsets, d_lengths, 0, count, d_ok,
-                                        layout, kernel, param, s, nullptr, hk)
-                  : tcpck::api::run_fixed(ctx, TCPCK_OP_VERIFY, mode, arena, stride, len, count, d_ok, kernel, param,
-                                          s, nullptr, hk);
+    e = tcpck::api::run(ctx, TCPCK_OP_VERIFY, mode,
+                        d_offsets ? Images::list(arena, d_offsets, d_lengths, 0, count, layout)
+                                  : Images::fixed(arena, stride, len, count),
+                        d_ok, kernel, param, s, nullptr, hk);
   const hipError_t e2 = hipEventRecord(ctx->join, ctx->side);
   const hipError_t e3 = e2 == hipSuccess ? hipStreamWaitEvent(s, ctx->join, 0) : e2;
   return hip_status(e != hipSuccess ? e : e3);

@@ -1,5 +1,5 @@
-// tcpck_internal.h -- private interface between the C-ABI layer (tcpck_api.hip)
-// and the gfx950 kernels (tcpck_kernels.hip, tcpck_rstream.hip, tcpck_vvstream.hip).
+// tcpck_internal.h -- private interface between the C-ABI layer (tcpck_api.hip,
+// tcpck_router.hip) and the gfx950 kernels (tcpck_kernels.hip, tcpck_rstream.hip, tcpck_vvstream.hip).
 // Not installed.
 #pragma once
 

@@ -1,7 +1,7 @@
 // tcpck_plan.h -- the batch router's policy as plain host code (no HIP,
 // tcpck_plan.cc): the layout predicates of the kernels, and the plan of one
 // batch -- which kernel runs with which param, and which passes go before and
-// after it -- that tcpck_api.hip launches from.  Included by tcpck_internal.h.
+// after it -- that tcpck_router.hip launches from.  Included by tcpck_internal.h.
 // Not installed.
 #pragma once
 

@@ -1,16 +1,20 @@
 // router_trace.cc -- the batch router's launches, recorded without a GPU.
 //
-// The router (tcpck::api::run_fixed / run_var, tcpck_api.hip + tcpck_plan.cc)
-// makes no HIP runtime call between its entry points and the tcpck::launch_*
-// functions, so this program links the router's objects with a recording
-// stand-in for every launcher of tcpck_internal.h and walks a fixed matrix of
-// requests through it on a fake context (num_cus = 256).  Each case is one
-// line: the inputs, the launches with every field of their argument structs
-// (pointers as offsets from this program's buffers), the returned hipError_t.
+// The router (tcpck::api::run, tcpck_router.hip + tcpck_plan.cc) makes no HIP
+// runtime call between its entry points and the tcpck::launch_* functions, so
+// this program links the router's objects with a recording stand-in for every
+// launcher of tcpck_internal.h and walks a fixed matrix of requests through it
+// on a fake context (num_cus = 256).  Each case is one line: the inputs, the
+// launches with every field of their argument structs (pointers as offsets
+// from this program's buffers), the returned hipError_t.
 //
 // Output (tests/golden/router_trace.txt, compared by tests/test_router_trace.py):
 //   F ... / V ...   one case of a fixed layout / an offset list, printed for a
 //                   small subset (`detailed` below);
+//   P ...           one FILL through the FILL front (tcpck::api::fill) as
+//                   batch_fixed_ex / batch_var_ex call it, whole batches and
+//                   the sub-ranges their scratch and pipeline chunks pass;
+//                   every case printed (sweep_fill_front);
 //   D ...           one group of the full matrix: the number of its cases and
 //                   the FNV-1a hash of ALL their lines, printed or not.
 // The full cartesian product of the layout axes is ~470,000 cases of 150-350
@@ -20,16 +24,26 @@
 //
 //   router_trace            the trace (the golden file)
 //   router_trace --all      every case's line
-//   router_trace --time     10^6 run_fixed AUTO FILL calls of the C2 shape
+//   router_trace --time     10^6 AUTO FILL calls of tcpck::api::run on the C2 shape
 //                           (1M x 1492-B packed images), recording off: ns per call
 //
 // Regenerating tests/golden/router_trace.txt: the file defines the router's
-// behaviour and was generated with the router's logic as it was before the
-// plan / launch split -- tcpck_api.hip of the parent of the commit that
-// introduced this program, which builds against this tree's headers:
-//   git show <that parent>:tcp-stack_amd/csrc/tcpck_api.hip > tcp-stack_amd/csrc/tcpck_api.hip
-//   make -C tcp-stack_amd trace && tests/cpp/build/router_trace > tests/golden/router_trace.txt
-//   git checkout tcp-stack_amd/csrc/tcpck_api.hip
+// behaviour and was generated on the router's OLD logic, never on the code it
+// checks.
+//   * The F, V and D lines of the first four sweeps: tcpck_api.hip as it was
+//     before the plan / launch split (the parent of the commit that introduced
+//     this program), built against that commit's headers, entered at
+//     run_fixed / run_var.
+//   * The P lines: the tree at the parent of the commit that introduced
+//     tcpck_router.hip, where one file, tcpck_api.hip, held the router with a
+//     fixed-layout and an offset-list copy of every function.  There
+//     `make -C tcp-stack_amd trace` links build/asan/tcpck_api.o, the F / V
+//     cases call run_fixed / run_var with the same arguments, and fill_cut
+//     below calls that tree's fill_fixed / fill_var (made reachable by two
+//     forwarding functions declared in tcpck_api_internal.h) with the values
+//     its batch_*_ex lambdas pass: arena + k0 * stride or offsets + k0 and
+//     lengths + k0, sub_layout(layout, n, count), the results pointer + k0.
+//     All earlier lines came out byte-identical in that run.
 // A change of the router that changes a line is a change of behaviour: extend
 // the matrix and regenerate on that old logic first, and only then change the
 // router.
@@ -60,6 +74,7 @@ alignas(64) uint32_t g_len[16];
 alignas(64) uint8_t g_stream[64];
 
 bool g_record = true;
+bool g_far_arena = false;  // group P only
 std::string g_launches;
 
 void add(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
@@ -82,6 +97,8 @@ std::string P(const void *p) {
     const auto at = reinterpret_cast<uintptr_t>(b.at);
     if (v >= at && v < at + 64) return std::string(b.name) + "+" + std::to_string(v - at);
   }
+  // group P: an arena pointer advanced to a later image of the batch
+  if (g_far_arena && v >= reinterpret_cast<uintptr_t>(g_arena)) return "a+" + std::to_string(v - reinterpret_cast<uintptr_t>(g_arena));
   return "?";
 }
 #define PS(p) P(p).c_str()
@@ -201,6 +218,7 @@ hipError_t launch_diag_stream(int variant, const uint8_t *buf, uint64_t bytes, u
 namespace {
 
 using tcpck::api::Hooks;
+using tcpck::api::Images;
 
 tcpck_ctx g_ctx;  // num_cus = 256, nothing else set
 const hipStream_t kStream = reinterpret_cast<hipStream_t>(g_stream);
@@ -285,9 +303,9 @@ void case_fixed(Group &g, const OpForm &f, int mode, uint64_t count, int align, 
            f.name, mode_name(mode), f.out, f.hdr, count, align, len, stride, kernel_name(kernel),
            static_cast<unsigned>(param), hk);
   g_launches.clear();
-  const hipError_t e = tcpck::api::run_fixed(&g_ctx, f.op, mode, g_arena + align, stride, len, count,
-                                             f.out ? g_out : nullptr, kernel, param, kStream, f.hdr ? g_hdr : nullptr,
-                                             hooks(hk));
+  const hipError_t e = tcpck::api::run(&g_ctx, f.op, mode, Images::fixed(g_arena + align, stride, len, count),
+                                       f.out ? g_out : nullptr, kernel, param, kStream, f.hdr ? g_hdr : nullptr,
+                                       hooks(hk));
   g.take(std::string(key) + g_launches + " = " + std::to_string(static_cast<int>(e)), detailed);
 }
 
@@ -314,8 +332,8 @@ void case_var(Group &g, const OpForm &f, int mode, uint64_t count, int align, co
            kernel_name(kernel), static_cast<unsigned>(param), hk);
   g_launches.clear();
   const hipError_t e =
-      tcpck::api::run_var(&g_ctx, f.op, mode, g_arena + align, g_off, g_len, base, count, f.out ? g_out : nullptr,
-                          l.null ? nullptr : &lay, kernel, param, kStream, f.hdr ? g_hdr : nullptr, hooks(hk));
+      tcpck::api::run(&g_ctx, f.op, mode, Images::list(g_arena + align, g_off, g_len, base, count, l.null ? nullptr : &lay),
+                      f.out ? g_out : nullptr, kernel, param, kStream, f.hdr ? g_hdr : nullptr, hooks(hk));
   g.take(std::string(key) + g_launches + " = " + std::to_string(static_cast<int>(e)), detailed);
 }
 
@@ -456,17 +474,114 @@ void sweep_hooks() {
     }
 }
 
+// ---- group P: the FILL front below the scratch decision ------------------------
+// tcpck::api::fill as batch_fixed_ex / batch_var_ex call it under AUTO with no
+// hooks (Hooks::fill_pipe == -1 and AUTO's chunk count 0: the front returns to
+// the serial form before any HIP call, so kStream never reaches the runtime):
+//   out=1          the batch with a results buffer;
+//   out=0 scr=0    without one, planned in-stream (no slot, or no field pass);
+//   out=0 scr=1    without one, planned as with a results buffer, the results
+//                  to a scratch slot (o+0): the batch, or the images
+//                  [k0, k0 + m) of it that one scratch chunk covers -- a later
+//                  chunk, a middle one, a last chunk of one image (in a gapped
+//                  layout planned on its own, as one packed image) -- and
+//                  [j0, j0 + m2) of those, the range a chunk of the pipelined
+//                  form passes on.
+// A list's byte hint is no multiple of its count, so the rounding of a
+// sub-range's hint (tb=) shows.
+struct Range {
+  uint64_t k0, n;  // n == 0: no cut
+};
+struct Cut {
+  Range r, r2;
+};
+
+std::vector<Cut> fill_cuts(uint64_t count, bool fixed) {
+  std::vector<Cut> c;
+  if (count > 2) c.push_back({{2, count - 2}, {0, 0}});
+  if (count == 1000) {
+    c.push_back({{3, 500}, {0, 0}});
+    c.push_back({{3, 500}, {4, 101}});
+    if (fixed) c.push_back({{count - 2, 2}, {1, 1}});
+  }
+  if (count == 2 || (fixed && count > 2)) c.push_back({{count - 1, 1}, {0, 0}});
+  return c;
+}
+
+hipError_t fill_cut(const tcpck::api::Plan &plan, int mode, const Images &whole, const Cut &c, uint16_t *out) {
+  Images im = whole;
+  if (c.r.n) im = im.sub(c.r.k0, c.r.n);
+  if (c.r2.n) {  // (a chunk's results follow its images)
+    im = im.sub(c.r2.k0, c.r2.n);
+    out += c.r2.k0;
+  }
+  return tcpck::api::fill(&g_ctx, plan, mode, im, out, TCPCK_KERNEL_AUTO, 0, kStream, Hooks{});
+}
+
+void case_fill(Group &g, int mode, const Images &whole, const char *shape, bool out, bool scr, const Cut &c) {
+  char key[320];
+  snprintf(key, sizeof key, "P %s mode=%s n=%" PRIu64 " out=%d scr=%d k0=%" PRIu64 " m=%" PRIu64 " j0=%" PRIu64
+           " m2=%" PRIu64 " ->",
+           shape, mode_name(mode), whole.count, out, scr, c.r.k0, c.r.n, c.r2.k0, c.r2.n);
+  const tcpck::api::Plan plan =
+      whole.offsets ? tcpck::api::plan_var(TCPCK_OP_FILL, mode, whole.layout, whole.count, out || scr, false,
+                                           TCPCK_KERNEL_AUTO, 0, Hooks{})
+                    : tcpck::api::plan_fixed(TCPCK_OP_FILL, mode, whole.arena, whole.stride, whole.len, whole.count,
+                                             out || scr, false, TCPCK_KERNEL_AUTO, 0, Hooks{});
+  g_launches.clear();
+  const hipError_t e = fill_cut(plan, mode, whole, c, out || scr ? reinterpret_cast<uint16_t *>(g_out) : nullptr);
+  g.take(std::string(key) + g_launches + " = " + std::to_string(static_cast<int>(e)), true);
+}
+
+void fill_cases(Group &g, int mode, const Images &whole, const char *shape, bool cuts) {
+  case_fill(g, mode, whole, shape, true, false, {});
+  case_fill(g, mode, whole, shape, false, false, {});
+  case_fill(g, mode, whole, shape, false, true, {});
+  if (cuts)
+    for (const Cut &c : fill_cuts(whole.count, !whole.offsets)) case_fill(g, mode, whole, shape, false, true, c);
+}
+
+void sweep_fill_front() {
+  g_far_arena = true;
+  Group g("P op=FILL k=AUTO hk=0");
+  for (const int mode : kModes)
+    for (const uint64_t count : {uint64_t{1}, uint64_t{2}, uint64_t{1000}, uint64_t{1} << 20}) {
+      if (mode != TCPCK_MODE_REF && count != 1000) continue;
+      for (const FixedShape &s : kReducedFixed) {
+        if (s.len < 30) continue;  // batch_fixed_ex rejects a FILL of shorter images
+        char shape[64];
+        snprintf(shape, sizeof shape, "fixed len=%u st=%" PRIu64, s.len, s.stride);
+        // (one image: its stride is never read, batch_fixed_ex passes stride = len)
+        fill_cases(g, mode, Images::fixed(g_arena, count == 1 ? s.len : s.stride, s.len, count), shape,
+                   mode == TCPCK_MODE_REF);
+      }
+      for (const Lay &l : kReducedVar) {
+        tcpck_layout lay{};
+        lay.total_bytes = l.typical * count + (count > 7 ? 7 : 0);
+        lay.min_len = l.min_len;
+        lay.max_len = l.max_len;
+        lay.flags = l.flags;
+        char shape[96];
+        snprintf(shape, sizeof shape, "list lay=%s fl=%u typ=%" PRIu64 " min=%u max=%u", l.null ? "null" : "hint", l.flags,
+                 l.typical, l.min_len, l.max_len);
+        fill_cases(g, mode, Images::list(g_arena, g_off, g_len, 0, count, l.null ? nullptr : &lay), shape,
+                   mode == TCPCK_MODE_REF);
+      }
+    }
+  g_far_arena = false;
+}
+
 int time_mode() {
   g_record = false;
   for (int rep = 0; rep < 2; ++rep) {  // the first round warms up
     const auto t0 = std::chrono::steady_clock::now();
     int bad = 0;
     for (int i = 0; i < 1000000; ++i)
-      bad += tcpck::api::run_fixed(&g_ctx, TCPCK_OP_FILL, TCPCK_MODE_REF, g_arena, 1492, 1492, 1u << 20, g_out,
-                                   TCPCK_KERNEL_AUTO, 0, kStream, nullptr, Hooks{}) != hipSuccess;
+      bad += tcpck::api::run(&g_ctx, TCPCK_OP_FILL, TCPCK_MODE_REF, Images::fixed(g_arena, 1492, 1492, 1u << 20), g_out,
+                             TCPCK_KERNEL_AUTO, 0, kStream, nullptr, Hooks{}) != hipSuccess;
     const double ns = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count();
     if (bad) return 1;
-    if (rep) printf("run_fixed AUTO FILL 1048576 x 1492 B: %.1f ns per call\n", ns / 1e6);
+    if (rep) printf("run AUTO FILL 1048576 x 1492 B: %.1f ns per call\n", ns / 1e6);
   }
   return 0;
 }
@@ -480,5 +595,6 @@ int main(int argc, char **argv) {
   sweep_var_auto();
   sweep_explicit();
   sweep_hooks();
+  sweep_fill_front();
   return 0;
 }

@@ -1,6 +1,6 @@
 """GPU parity: the pipelined FILL and the round-6 router fixes.
 
-Pipelined FILL (tcp-stack_amd/csrc/tcpck_api.hip fill_pipelined, VERDICT r05
+Pipelined FILL (tcp-stack_amd/csrc/tcpck_router.hip fill_pipelined, VERDICT r05
 item 1; reached through the probe library's tcpck_batch_*_ex under
 TCPCK_KERNEL_AUTO after tcpck_probe_set_fill_pipe): the batch in K chunks, the field pass of chunk i on a context stream
 beside the stream pass of chunk i + 1.  Whatever K, the bytes must be the

@@ -2,7 +2,8 @@
 
 tests/cpp/router_trace.cc links the router's host objects with recording
 stand-ins for every kernel launcher and walks a fixed matrix of requests
-through tcpck::api::run_fixed / run_var; tests/golden/router_trace.txt is its
+through tcpck::api::run (and, group P, the FILL front tcpck::api::fill);
+tests/golden/router_trace.txt is its
 output on the router as it stood before the plan / launch split.  Every
 launch, every field of its arguments and every returned status must stay as
 recorded: a differing line is a change of behaviour, not something to
