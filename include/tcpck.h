@@ -167,6 +167,97 @@ int tcpck_batch_set_ack(tcpck_ctx *ctx, int mode, void *d_arena, const uint64_t 
                         uint64_t stride, uint64_t count, const uint32_t *d_acks, uint32_t ack,
                         uint16_t *d_out, tcpck_stream stream);
 
+/* ---- batched resend pass: ResendPredicate over a whole send queue ---------
+ * The reference's resend event, per queued packet:
+ * SocketManager::InternalSendPacketWithResend (include/socket-manager.h:37-51)
+ * calls SocketInternal::ResendPredicate::operator()
+ * (include/socket-internal.h:363-390), which rewrites the ACK number to
+ * htonl(rcv_nxt) (:376-377), decides from snd_una, the packet's sequence number
+ * and its SYN / FIN bits whether the packet is still owed (:378-385; a dead
+ * socket, :371-373, or a closed one, :379-380, drops it), and then either sends
+ * the packet again through SendPacket (src/socket-manager.cc:6-12: the checksum
+ * recomputed) and re-queues it, or drops it from the queue.  Here, for a queue
+ * of many connections in one call: a predicate per image, tcpck_batch_set_ack's
+ * 6-byte patch on the survivors, and a stable compaction of the queue's
+ * descriptor arrays.  The dense (offsets, lengths) list of the survivors is the
+ * retransmit ring -- already what tcpck_batch_var / tcpck_batch_receive take,
+ * TCPCK_LAYOUT_SORTED preserved because the compaction is stable -- and the
+ * queue of the next pass.
+ *
+ * Image k: at k * stride, `len` bytes (d_offsets == NULL), else at d_offsets[k],
+ * d_lengths[k] bytes.  Its connection: c = d_conn ? d_conn[k] : 0.  d_snd: one
+ * tcpck_snd_state per connection, n_conns of them, refreshed by the caller.
+ *   dropped untouched (keep = 0, not one byte of the image written): an odd
+ *     offset or length; a length below 32; a range that does not fit in
+ *     [0, arena_bytes); c >= n_conns -- the dead weak_ptr of :371-373,
+ *     TCPCK_CONN_NONE lands here, and no state block outside [0, n_conns) is
+ *     read, whatever the arrays hold; d_snd[c].flags & TCPCK_SND_CLOSED
+ *     (:379-380).  The reference rewrites the ACK number before it looks at the
+ *     closed state and then destroys the packet: that rewrite is unobservable,
+ *     so here the image stays as it was.
+ *   read from the header: seq = the big-endian u32 at bytes 16-19
+ *     (ntohl(SequenceNumber())); byte 25's SYN 0x40 and FIN 0x80.
+ *   TCPCK_RESEND_REF (:381-385): keep iff snd_una < seq + 1 for a SYN or FIN
+ *     image (u32: 0xFFFFFFFF + 1 is 0), iff snd_una < seq otherwise.  Plain
+ *     unsigned compares, as the reference, with its consequences kept: a data
+ *     image whose seq == snd_una is dropped (wholly unacknowledged as it is), and
+ *     nothing is kept across a wrap of snd_una (snd_una just below 2^32, seq
+ *     just above 0: dropped).
+ *   TCPCK_RESEND_SERIAL (opt-in, like TCPCK_MODE_RFC1071; NOT what the
+ *     reference computes): n = TcpLength (the big-endian u16 at bytes 10-11) + 1
+ *     for a SYN or FIN image; keep iff n > 0 and (int32_t)(seq + n - snd_una) >
+ *     0 -- RFC 793 serial arithmetic: some sequence number of the image is not
+ *     yet acknowledged.
+ *   kept: bytes 20-23 := htonl(d_snd[c].rcv_nxt) and bytes 28-29 updated from
+ *     the old and new words exactly as tcpck_batch_set_ack does in `mode` -- the
+ *     reference's full recompute whenever the stored checksum was valid.  No
+ *     other byte of the arena changes.  The call equals tcpck_batch_set_ack on
+ *     exactly the kept images, each image's ack its connection's rcv_nxt.
+ * Outputs, each of the five arrays may be NULL: d_keep[k] = 0 or 1; the
+ * survivors dense and in queue order: d_out_offsets[j], d_out_lengths[j],
+ * d_out_conn[j] (0 when d_conn is NULL), d_src[j] = k; *d_count (device, u64) =
+ * the number kept.  When that exceeds out_cap only the first out_cap entries of
+ * each list are written, *d_count still holds the total and every kept image is
+ * still patched; the patch is idempotent under the same d_snd, so a caller that
+ * ran short runs again with longer lists.  Nothing is written past any list's
+ * min(total, out_cap) entries or past d_keep[count).  Preconditions: the images
+ * of a queue are disjoint; the output lists overlap neither the input lists nor
+ * each other (to iterate, ping-pong two sets of lists).  d_scratch: device
+ * memory of the size tcpck_resend_scratch_bytes(count, &bytes) gives (never 0),
+ * its contents undefined before and after.  Asynchronous on `stream`; nothing is
+ * allocated; no host synchronisation; the same inputs give the same bytes.
+ * count == 0 is TCPCK_OK and sets *d_count = 0 in stream order when d_count is
+ * not NULL.  TCPCK_EINVAL, nothing launched or written: ctx NULL; a bad mode or
+ * rule; count > 2^31; with count > 0 a NULL d_arena, d_snd (when n_conns > 0),
+ * d_count or d_scratch; d_offsets and d_lengths not both NULL or both set; the
+ * fixed form with an odd stride or len, len < 32 or stride < len; a misaligned
+ * pointer (d_arena 2-B; the u32 arrays 4-B; the u64 arrays and d_count 8-B;
+ * d_snd and d_scratch 16-B).  tcpck_resend_scratch_bytes: TCPCK_EINVAL for
+ * bytes NULL or count > 2^31. */
+typedef struct tcpck_snd_state {      /* 16 B per connection: what ResendPredicate reads */
+  uint32_t snd_una, rcv_nxt, flags, reserved;
+} tcpck_snd_state;
+#define TCPCK_SND_CLOSED 1u           /* state_.GetState() == State::kClosed */
+#define TCPCK_RESEND_REF 0            /* the reference's compare, bit for bit */
+#define TCPCK_RESEND_SERIAL 1         /* opt-in: RFC 793 serial arithmetic */
+int tcpck_resend_scratch_bytes(uint64_t count, size_t *bytes);
+int tcpck_batch_resend(tcpck_ctx *ctx, int mode, int rule, void *d_arena, uint64_t arena_bytes,
+                       uint64_t stride, uint32_t len, const uint64_t *d_offsets, const uint32_t *d_lengths,
+                       const uint32_t *d_conn, const tcpck_snd_state *d_snd, uint32_t n_conns, uint64_t count,
+                       uint8_t *d_keep, uint64_t *d_out_offsets, uint32_t *d_out_lengths, uint32_t *d_out_conn,
+                       uint32_t *d_src, uint64_t out_cap, uint64_t *d_count, void *d_scratch, tcpck_stream stream);
+/* The same contract on host memory: plain host C++, reentrant, no device, no
+ * scratch; the number kept is returned through n_kept.  The CPU fallback and the
+ * second implementation the device call is tested against.  It checks the same
+ * clauses (n_kept in d_count's place); every case a host could see in the
+ * arrays' contents is, by the rule above, a dropped image and not an error.
+ * Nothing is written on an error. */
+int tcpck_resend_images(int mode, int rule, void *h_arena, uint64_t arena_bytes, uint64_t stride, uint32_t len,
+                        const uint64_t *h_offsets, const uint32_t *h_lengths, const uint32_t *h_conn,
+                        const tcpck_snd_state *h_snd, uint32_t n_conns, uint64_t count, uint8_t *h_keep,
+                        uint64_t *h_out_offsets, uint32_t *h_out_lengths, uint32_t *h_out_conn, uint32_t *h_src,
+                        uint64_t out_cap, uint64_t *n_kept);
+
 /* ---- batched header byte order: TcpHeaderN2H / TcpHeaderH2N -------------
  * ReceivePacket verifies the network-order image and then converts its header
  * to host order (include/socket-manager.h:182-184); TcpHeaderN2H and

@@ -182,6 +182,25 @@ __device__ __forceinline__ uint16_t finish(uint32_t sum) {
   }
 }
 
+// The stored checksum c after the two u16 words of the ACK number (bytes 20-23)
+// change from o0, o1 to n0, n1 (tcpck_resend.hip states the two formulas): the
+// retransmit kernels' incremental update, equal to the full recompute whenever c
+// was the valid checksum of the old image.
+template <int MODE>
+__device__ __forceinline__ uint16_t update_ack(uint16_t c, uint16_t o0, uint16_t o1, uint16_t n0, uint16_t n1) {
+  if constexpr (MODE == kRef) {
+    const uint32_t s = static_cast<uint16_t>(~c) - o0 - o1 + n0 + n1;
+    return static_cast<uint16_t>(~s);
+  } else {
+    uint32_t s = static_cast<uint32_t>(static_cast<uint16_t>(~c)) + static_cast<uint16_t>(~o0) +
+                 static_cast<uint16_t>(~o1) + n0 + n1;
+    s = (s & 0xFFFFu) + (s >> 16);
+    s = (s & 0xFFFFu) + (s >> 16);
+    if (s == 0) s = 0xFFFFu;
+    return static_cast<uint16_t>(~s);
+  }
+}
+
 template <int G>
 __device__ __forceinline__ uint32_t group_sum(uint32_t x) {
 #pragma unroll

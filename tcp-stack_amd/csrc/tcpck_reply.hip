@@ -22,8 +22,8 @@
 //          kReplyChunks chunks of 64 per wave: the reply predicate (verdict
 //          byte, and for an ACK the connection id against n_conns), a wave
 //          ballot per chunk, the block's total into d_scratch[block];
-//   scan   ONE block of kScanBlock threads turns the block totals into
-//          exclusive offsets in place, kScanBlock totals per step with a
+//   scan   (tcpck_compact.h, shared with tcpck_resend_queue.hip) ONE block of
+//          kScanBlock threads turns the block totals into exclusive offsets in place, kScanBlock totals per step with a
 //          running carry (the loop is bounded by the block count, a launch
 //          argument), and stores the grand total to *d_count;
 //   emit   the count pass's predicate again; a replying lane's index is
@@ -41,6 +41,7 @@
 #include <algorithm>
 
 #include "tcpck_api_internal.h"
+#include "tcpck_compact.h"
 #include "tcpck_device.h"
 #include "tcpck_reply.h"
 
@@ -50,12 +51,11 @@ namespace {
 
 using dev::u32x4;
 
-constexpr uint32_t kReplyBlock = 256;
-constexpr uint32_t kReplyWaves = kReplyBlock / 64;
-constexpr uint32_t kReplyChunks = reply::kImagesPerBlock / kReplyBlock;  // chunks of 64 images per wave
-constexpr uint32_t kScanBlock = 1024;
-constexpr uint32_t kScanWaves = kScanBlock / 64;
-static_assert(reply::kImagesPerBlock == kReplyBlock * kReplyChunks, "a block is whole chunks");
+// the compaction's geometry, scan and index arithmetic: tcpck_compact.h
+constexpr uint32_t kReplyBlock = compact::kBlock;
+constexpr uint32_t kReplyWaves = compact::kWaves;
+constexpr uint32_t kReplyChunks = compact::kChunks;  // chunks of 64 images per wave
+using compact::lanes_below;
 
 constexpr uint32_t kNone = 0, kAck = 1, kRst = 2;
 
@@ -71,57 +71,18 @@ __device__ __forceinline__ uint32_t reply_kind(const uint8_t *__restrict__ verdi
   return c < n_conns ? kAck : kNone;  // (TCPCK_CONN_NONE is >= every n_conns)
 }
 
-__device__ __forceinline__ uint32_t lanes_below(uint64_t ballot) {
-  return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(ballot >> 32),
-                                   __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(ballot), 0u));
-}
-
 __global__ void __launch_bounds__(kReplyBlock) reply_count_kernel(const uint8_t *__restrict__ verdict,
                                                                   const uint32_t *__restrict__ conn, uint32_t n_conns,
                                                                   uint32_t count, uint32_t *__restrict__ totals) {
   __shared__ uint32_t wave_total[kReplyWaves];
-  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  const uint32_t first = blockIdx.x * reply::kImagesPerBlock + w * (64u * kReplyChunks) + lane;
+  const uint32_t first = compact::first_image();
   uint32_t n = 0;
 #pragma unroll
   for (uint32_t i = 0; i < kReplyChunks; ++i) {
     uint32_t c;
     n += __popcll(__ballot(reply_kind(verdict, conn, n_conns, first + 64u * i, count, c) != kNone));
   }
-  if (lane == 0) wave_total[w] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < kReplyWaves; ++i) t += wave_total[i];
-    totals[blockIdx.x] = t;
-  }
-}
-
-// One block.  totals[0, nblocks) -> exclusive prefix sums in place; *total = the sum.
-__global__ void __launch_bounds__(kScanBlock) reply_scan_kernel(uint32_t *__restrict__ totals, uint32_t nblocks,
-                                                                uint64_t *__restrict__ total) {
-  __shared__ uint32_t wave_sum[kScanWaves];
-  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  uint32_t carry = 0;  // (at most 2^31 replies: u32 holds every offset)
-  for (uint32_t base = 0; base < nblocks; base += kScanBlock) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t v = i < nblocks ? totals[i] : 0u;
-    const uint32_t incl = dev::wave_inclusive_scan(v);
-    if (lane == 63) wave_sum[w] = incl;
-    __syncthreads();
-    uint32_t before = 0, step = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kScanWaves; ++j) {
-      const uint32_t s = wave_sum[j];
-      before += j < w ? s : 0u;
-      step += s;
-    }
-    if (i < nblocks) totals[i] = carry + before + incl - v;
-    carry += step;
-    __syncthreads();  // wave_sum is rewritten by the next step
-  }
-  if (threadIdx.x == 0) *total = carry;
+  compact::store_block_total(wave_total, n, totals);
 }
 
 template <int MODE>
@@ -149,8 +110,7 @@ __global__ void __launch_bounds__(kReplyBlock)
                       uint32_t count, const uint32_t *__restrict__ offsets, uint8_t *__restrict__ replies,
                       uint64_t reply_cap, uint32_t *__restrict__ src) {
   __shared__ uint32_t wave_total[kReplyWaves];
-  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  const uint32_t first = blockIdx.x * reply::kImagesPerBlock + w * (64u * kReplyChunks) + lane;
+  const uint32_t first = compact::first_image();
   uint32_t kind[kReplyChunks], c[kReplyChunks];
   uint64_t ballot[kReplyChunks];
   uint32_t n = 0;
@@ -160,11 +120,7 @@ __global__ void __launch_bounds__(kReplyBlock)
     ballot[i] = __ballot(kind[i] != kNone);
     n += __popcll(ballot[i]);
   }
-  if (lane == 0) wave_total[w] = n;
-  __syncthreads();
-  uint32_t at = offsets[blockIdx.x];  // replies before this block
-#pragma unroll
-  for (uint32_t i = 0; i < kReplyWaves; ++i) at += i < w ? wave_total[i] : 0u;
+  uint32_t at = offsets[blockIdx.x] + compact::waves_before(wave_total, n);  // replies before this block, this wave
 #pragma unroll
   for (uint32_t i = 0; i < kReplyChunks; ++i) {
     const uint32_t k = first + 64u * i;
@@ -203,8 +159,7 @@ static hipError_t launch_reply(int mode, const uint8_t *d_verdict, const uint32_
                      d_scratch);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(reply_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, d_scratch, blocks, d_count);
-  e = hipGetLastError();
+  e = compact::launch_scan_totals(d_scratch, blocks, d_count, stream);
   if (e != hipSuccess) return e;
   if (mode == TCPCK_MODE_REF) {
     hipLaunchKernelGGL(reply_emit_kernel<kRef>, dim3(blocks), dim3(kReplyBlock), 0, stream, d_verdict, d_ack, d_conn,

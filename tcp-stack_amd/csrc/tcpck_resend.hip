@@ -25,21 +25,7 @@ namespace tcpck {
 namespace {
 
 using dev::kBlock;
-
-template <int MODE>
-__device__ __forceinline__ uint16_t update_ack(uint16_t c, uint16_t o0, uint16_t o1, uint16_t n0, uint16_t n1) {
-  if constexpr (MODE == kRef) {
-    const uint32_t s = static_cast<uint16_t>(~c) - o0 - o1 + n0 + n1;
-    return static_cast<uint16_t>(~s);
-  } else {
-    uint32_t s = static_cast<uint32_t>(static_cast<uint16_t>(~c)) + static_cast<uint16_t>(~o0) +
-                 static_cast<uint16_t>(~o1) + n0 + n1;
-    s = (s & 0xFFFFu) + (s >> 16);
-    s = (s & 0xFFFFu) + (s >> 16);
-    if (s == 0) s = 0xFFFFu;
-    return static_cast<uint16_t>(~s);
-  }
-}
+using dev::update_ack;  // (shared with tcpck_resend_queue.hip)
 
 template <int MODE, bool FIXED, bool PER_IMAGE>
 __global__ void __launch_bounds__(kBlock) set_ack_kernel(AckArgs a) {

@@ -67,6 +67,11 @@ RCV_RST = 16      # no socket, good sum: reply RST, seq = ack[k] (the image's ac
 RCV_HOST = 32     # not decided here: the host path takes the image, in arrival order
 REPLY_BYTES = 32  # one reply of tcpck_batch_reply / tcpck_build_replies: a header, no payload
 
+# batched resend pass (tcpck_batch_resend / tcpck_resend_images)
+SND_CLOSED = 1     # SndState.flags: state_.GetState() == State::kClosed
+RESEND_REF = 0     # the reference's compare (socket-internal.h:381-385), bit for bit
+RESEND_SERIAL = 1  # opt-in: RFC 793 serial arithmetic
+
 # include/tcpck_tuning.h
 KERNEL_AUTO = 0
 KERNEL_SEG = 1    # param: seg shape + 1 (1..11, SEG_SHAPES), 0 = by length
@@ -143,6 +148,7 @@ EXPORTS = (
     "tcpck_conn_table_find", "tcpck_conn_table_commit", "tcpck_conn_table_stats", "tcpck_batch_demux",
     "tcpck_plan_deliver_multi",
     "tcpck_reply_scratch_bytes", "tcpck_batch_reply", "tcpck_build_replies",
+    "tcpck_resend_scratch_bytes", "tcpck_batch_resend", "tcpck_resend_images",
 )
 
 
@@ -171,6 +177,13 @@ class ConnState(ctypes.Structure):
     its walk stopped (out) and CONN_ESTAB / CONN_HOST."""
     _fields_ = [("rcv", RcvState), ("recv_base", ctypes.c_uint64), ("recv_bytes", ctypes.c_uint64),
                 ("stopped_at", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class SndState(ctypes.Structure):
+    """tcpck_snd_state: what ResendPredicate reads of a connection (socket-internal.h:363-390):
+    snd_una, rcv_nxt and SND_CLOSED in flags.  16 bytes; a numpy table of them is uint32[n, 4]."""
+    _fields_ = [("snd_una", ctypes.c_uint32), ("rcv_nxt", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
 
 
 _libs: dict = {}
@@ -235,6 +248,11 @@ def lib(probe: bool = False) -> ctypes.CDLL:
         "tcpck_reply_scratch_bytes": (i32, [u64, ctypes.POINTER(sz)]),
         "tcpck_batch_reply": (i32, [vp, i32, vp, vp, vp, vp, u32, u64, vp, u64, vp, vp, vp, vp]),
         "tcpck_build_replies": (i32, [i32, vp, vp, vp, vp, u32, u64, vp, u64, vp, ctypes.POINTER(u64)]),
+        "tcpck_resend_scratch_bytes": (i32, [u64, ctypes.POINTER(sz)]),
+        "tcpck_batch_resend": (i32, [vp, i32, i32, vp, u64, u64, u32, vp, vp, vp, vp, u32, u64, vp, vp, vp, vp, vp, u64,
+                                     vp, vp, vp]),
+        "tcpck_resend_images": (i32, [i32, i32, vp, u64, u64, u32, vp, vp, vp, vp, u32, u64, vp, vp, vp, vp, vp, u64,
+                                      ctypes.POINTER(u64)]),
         # include/tcpck_tuning.h
         "tcpck_batch_fixed_ex": (i32, [vp, i32, i32, vp, u64, u32, u64, vp, i32, i32, vp]),
         "tcpck_batch_var_ex": (i32, [vp, i32, i32, vp, vp, vp, u64, vp, ctypes.POINTER(Layout), i32, i32, vp]),
@@ -430,6 +448,51 @@ def build_replies(verdict, ack, tmpl, conn=None, reply_cap: int | None = None, m
     return replies[:32 * written].reshape(-1, 32), src[:written], total.value
 
 
+def resend_scratch_bytes(count: int) -> int:
+    """Bytes of device scratch Context.batch_resend needs for a queue of `count` images (never 0)."""
+    out = ctypes.c_size_t()
+    _check(lib().tcpck_resend_scratch_bytes(count, ctypes.byref(out)), "tcpck_resend_scratch_bytes")
+    return out.value
+
+
+def resend_images(arena, snd, count: int | None = None, stride: int = 0, length: int = 0, offsets=None, lengths=None,
+                  conn=None, out_cap: int | None = None, rule: int = RESEND_REF, mode: int = MODE_REF):
+    """tcpck_resend_images on numpy arrays (host only, no device): the reference's resend event
+    (ResendPredicate, socket-internal.h:363-390) over a whole send queue.  arena: writable uint8, the
+    kept images are patched in place (ACK number := htonl(rcv_nxt), checksum updated).  snd: uint32[n_conns,
+    4] rows of (snd_una, rcv_nxt, flags, reserved); conn: uint32 ids (None: every image is connection 0).
+    Fixed layout (count, stride, length) or offsets + lengths.  Returns (keep u8[count], out_offsets
+    u64[w], out_lengths u32[w], out_conn u32[w], src u32[w], total): the survivors dense and in queue
+    order, w = min(total, out_cap) (out_cap None: the image count)."""
+    import numpy as np
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        n = offsets.size
+        if lengths.size != n:
+            raise ValueError("lengths must hold one entry per image")
+    else:
+        n = int(count)
+    snd = np.ascontiguousarray(snd, dtype=np.uint32).reshape(-1, 4)
+    if conn is not None:
+        conn = np.ascontiguousarray(conn, dtype=np.uint32)
+        if conn.size != n:
+            raise ValueError("conn must hold one entry per image")
+    if not (arena.dtype == np.uint8 and arena.flags.c_contiguous and arena.flags.writeable):
+        raise ValueError("arena must be a writable contiguous uint8 array")
+    cap = n if out_cap is None else out_cap
+    keep = np.zeros(n + 1, np.uint8)  # (one element more: never an empty array's NULL)
+    out_off, out_len = np.zeros(cap + 1, np.uint64), np.zeros(cap + 1, np.uint32)
+    out_conn, src = np.zeros(cap + 1, np.uint32), np.zeros(cap + 1, np.uint32)
+    total = ctypes.c_uint64()
+    _check(lib().tcpck_resend_images(mode, rule, arena.ctypes.data, arena.size, stride, length, _ptr(offsets),
+                                     _ptr(lengths), _ptr(conn), snd.ctypes.data if snd.size else None, snd.shape[0], n,
+                                     keep.ctypes.data, out_off.ctypes.data, out_len.ctypes.data, out_conn.ctypes.data,
+                                     src.ctypes.data, cap, ctypes.byref(total)), "tcpck_resend_images")
+    w = min(total.value, cap)
+    return keep[:n], out_off[:w], out_len[:w], out_conn[:w], src[:w], total.value
+
+
 class ConnTable:
     """tcpck_conn_table: ReceivePacket's socket map (socket-manager.h:187-196, 235-245) as a host
     mirror plus a device image batch_demux probes.  Keys are (host_port, peer_ip, peer_port), a
@@ -592,6 +655,22 @@ class Context:
         _check(self._L.tcpck_batch_reply(self._h, mode, _ptr(verdict), _ptr(ack), _ptr(conn), _ptr(tmpl), n_conns, count,
                                          _ptr(replies), reply_cap, _ptr(src), _ptr(total), _ptr(scratch),
                                          _stream(stream)), "tcpck_batch_reply")
+
+    def batch_resend(self, arena, arena_bytes: int, snd, n_conns: int, count: int, total, scratch, stride: int = 0,
+                     length: int = 0, offsets=None, lengths=None, conn=None, keep=None, out_offsets=None,
+                     out_lengths=None, out_conn=None, src=None, out_cap: int = 0, rule: int = RESEND_REF,
+                     mode: int = MODE_REF, stream=None) -> None:
+        """The reference's resend event over a whole send queue (tcpck_batch_resend; ResendPredicate,
+        socket-internal.h:363-390): device arrays; image k at k * stride (`length` bytes) or at offsets[k]
+        (lengths[k] bytes), its connection conn[k] (None: 0), snd 16 B of (snd_una, rcv_nxt, flags,
+        reserved) per connection.  Kept images get ACK number := htonl(rcv_nxt) and the checksum updated in
+        place; keep[k] (u8), the survivors' out_offsets (u64) / out_lengths / out_conn / src (u32) dense
+        and in queue order for j < out_cap (each may be None), total (one u64) the number kept; scratch:
+        resend_scratch_bytes(count) bytes of device memory."""
+        _check(self._L.tcpck_batch_resend(self._h, mode, rule, _ptr(arena), arena_bytes, stride, length, _ptr(offsets),
+                                          _ptr(lengths), _ptr(conn), _ptr(snd), n_conns, count, _ptr(keep),
+                                          _ptr(out_offsets), _ptr(out_lengths), _ptr(out_conn), _ptr(src), out_cap,
+                                          _ptr(total), _ptr(scratch), _stream(stream)), "tcpck_batch_resend")
 
     def batch_segment(self, payload, payload_bytes: int, seg: int, hdr, seq0: int, images, stride: int,
                       out=None, mode: int = MODE_REF, param: int | None = None, stream=None) -> int:
