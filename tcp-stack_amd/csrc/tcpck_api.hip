@@ -226,10 +226,7 @@ int tcpck_batch_set_ack(tcpck_ctx *ctx, int mode, void *d_arena, const uint64_t 
   DeviceGuard g(ctx->device);
   if (g.status() != hipSuccess) return hip_status(g.status());
   tcpck::AckArgs a{};
-  a.arena = static_cast<uint8_t *>(d_arena);
-  a.offsets = d_offsets;
-  a.stride = stride;
-  a.count = count;
+  a.im = {static_cast<uint8_t *>(d_arena), d_offsets, nullptr, stride, 0, count, 0};
   a.acks = d_acks;
   a.ack = ack;
   a.out = d_out;
@@ -256,10 +253,7 @@ int tcpck_batch_header_swap(tcpck_ctx *ctx, void *d_arena, const uint64_t *d_off
   DeviceGuard g(ctx->device);
   if (g.status() != hipSuccess) return hip_status(g.status());
   tcpck::HeaderArgs a{};
-  a.arena = static_cast<uint8_t *>(d_arena);
-  a.offsets = d_offsets;
-  a.stride = stride;
-  a.count = count;
+  a.im = {static_cast<uint8_t *>(d_arena), d_offsets, nullptr, stride, 0, count, 0};
   return hip_status(tcpck::launch_header_swap(a, static_cast<uint32_t>(ctx->num_cus),
                                               static_cast<hipStream_t>(stream)));
 }

@@ -8,7 +8,8 @@
 // product's kernel policy and nothing else) and launches the plan; the probe
 // library passes it a Hooks value to reach the measured alternatives (header
 // pass forms, fused headers on explicit kernels), the product library always
-// passes Hooks{}.
+// passes Hooks{}.  A batch's images travel as one Images value: the ImageSpan
+// the launchers take (tcpck_internal.h) and the host-only layout hints.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,6 +19,7 @@
 #include <mutex>
 
 #include "tcpck.h"
+#include "tcpck_internal.h"
 #include "tcpck_plan.h"
 
 struct tcpck_ctx {
@@ -128,30 +130,20 @@ class DeviceGuard {
   hipError_t ok_ = hipSuccess;
 };
 
-// Where a batch's images are: `count` images of `len` bytes every `stride`
-// bytes from `arena` (the fixed layout: offsets and lengths null, base 0), or
-// image k at arena + offsets[k] - base with lengths[k] bytes (an offset list:
-// stride and len 0), with the caller's layout hint or nullptr.
-struct Images {
-  uint8_t *arena = nullptr;
-  const uint64_t *offsets = nullptr;
-  const uint32_t *lengths = nullptr;
-  uint64_t stride = 0;
-  uint32_t len = 0;
-  uint64_t base = 0;
-  uint64_t count = 0;
-  const tcpck_layout *layout = nullptr;
-  uint64_t total_bytes = 0;  // these images' share of layout->total_bytes (sub)
-  bool lone = false;         // one image cut from a gapped fixed layout (sub): the batch's plan is not its plan
+// Where a batch's images are (ImageSpan, tcpck_internal.h: what the launchers
+// take), with what only the host reads: the caller's layout hint or nullptr.
+struct Images : ImageSpan {
+  const tcpck_layout *layout;
+  uint64_t total_bytes;  // these images' share of layout->total_bytes (sub)
+  bool lone;             // one image cut from a gapped fixed layout (sub): the batch's plan is not its plan
 
   static Images fixed(uint8_t *arena, uint64_t stride, uint32_t len, uint64_t count) {
-    return {arena, nullptr, nullptr, stride, len, 0, count, nullptr, 0, false};
+    return {{arena, nullptr, nullptr, stride, 0, count, len}, nullptr, 0, false};
   }
   static Images list(uint8_t *arena, const uint64_t *offsets, const uint32_t *lengths, uint64_t base, uint64_t count,
                      const tcpck_layout *layout) {
-    return {arena, offsets, lengths, 0, 0, base, count, layout, layout ? layout->total_bytes : 0, false};
+    return {{arena, offsets, lengths, 0, base, count, 0}, layout, layout ? layout->total_bytes : 0, false};
   }
-  bool is_fixed() const { return !offsets; }
 
   // Images [k0, k0 + n).  An offset list keeps the flags and the length bounds
   // of its hint, and its byte hint scales with its image count, so its typical

@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(64 * W) deliver_kernel(DeliverArgs a) {
   uint64_t kb, ke;
   dev::count_split(bid, a.per_block, a.rem, kb, ke);
   if (kb >= ke) return;
-  const uint64_t arena = reinterpret_cast<uint64_t>(a.arena);
+  const uint64_t arena = reinterpret_cast<uint64_t>(static_cast<const uint8_t *>(a.im.arena));
 
   // image kb + lane's descriptor; invalid ones come back with ln = 0
   auto descriptor = [&](uint64_t k, uint64_t &off, uint32_t &ln, uint64_t &d) {
@@ -94,8 +94,8 @@ __global__ void __launch_bounds__(64 * W) deliver_kernel(DeliverArgs a) {
     if (k < ke) {
       d = a.dst[k];
       if (d != TCPCK_DELIVER_SKIP) {
-        off = a.offsets ? a.offsets[k] : k * a.stride;
-        ln = a.lengths ? a.lengths[k] : a.len;
+        off = a.im.start(k);
+        ln = a.im.length(k);
       }
     }
   };
@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(64 * W) deliver_kernel(DeliverArgs a) {
 
 hipError_t launch_deliver(DeliverArgs a, uint32_t num_cus, uint64_t run_forced, uint64_t max_blocks_forced,
                           uint64_t *split, hipStream_t stream) {
-  if (a.count == 0) return hipSuccess;
+  if (a.im.count == 0) return hipSuccess;
   constexpr int W = kDeliverWaves, U = 4;
   static const uint32_t per_cu = [] {
     int nb = 0;
@@ -251,11 +251,11 @@ hipError_t launch_deliver(DeliverArgs a, uint32_t num_cus, uint64_t run_forced, 
   const uint64_t resident = static_cast<uint64_t>(per_cu) * num_cus;
   // (tests force either through the probe library to reach the group walk at small counts)
   const uint64_t run =
-      run_forced ? run_forced : std::min<uint64_t>(64, std::max<uint64_t>(1, a.count / (resident * 4)));
+      run_forced ? run_forced : std::min<uint64_t>(64, std::max<uint64_t>(1, a.im.count / (resident * 4)));
   const uint64_t cap = max_blocks_forced ? max_blocks_forced : resident * 64;
-  const uint64_t blocks = std::min<uint64_t>(a.count / run + (a.count % run != 0), cap);
-  a.per_block = a.count / blocks;
-  a.rem = a.count % blocks;
+  const uint64_t blocks = std::min<uint64_t>(a.im.count / run + (a.im.count % run != 0), cap);
+  a.per_block = a.im.count / blocks;
+  a.rem = a.im.count % blocks;
   if (split) split[0] = blocks, split[1] = a.per_block, split[2] = a.rem;
   a.order = 4u;  // groups of 16 blocks per XCD
   hipLaunchKernelGGL((deliver_kernel<W, U>), dim3(static_cast<uint32_t>(blocks)), dim3(64 * W), 0, stream, a);
@@ -283,14 +283,10 @@ extern "C" int tcpck_batch_deliver(tcpck_ctx *ctx, const void *d_arena, uint64_t
   DeviceGuard g(ctx->device);
   if (g.status() != hipSuccess) return hip_status(g.status());
   tcpck::DeliverArgs a{};
-  a.arena = static_cast<const uint8_t *>(d_arena);
-  a.offsets = d_offsets;
-  a.lengths = d_lengths;
+  // (the span's arena is shared with the launchers that write; this kernel only reads through it)
+  a.im = {static_cast<uint8_t *>(const_cast<void *>(d_arena)), d_offsets, d_lengths, stride, 0, count, len};
   a.dst = d_dst;
   a.recv = static_cast<uint8_t *>(d_recv);
-  a.stride = stride;
-  a.len = len;
-  a.count = count;
   a.recv_bytes = recv_bytes;
 #ifdef TCPCK_PROBE  // the probe library: the grid a test set, and the split it reads back
   return hip_status(tcpck::launch_deliver(a, static_cast<uint32_t>(ctx->num_cus), ctx->probe_deliver_run,

@@ -77,9 +77,7 @@ int tcpck_batch_fixed_ex(tcpck_ctx *ctx, int op, int mode, void *d_arena, uint64
     DeviceGuard g(ctx->device);
     if (g.status() != hipSuccess) return hip_status(g.status());
     tcpck::PatchArgs pa{};
-    pa.arena = static_cast<uint8_t *>(d_arena);
-    pa.stride = stride;
-    pa.count = count;
+    pa.im = {static_cast<uint8_t *>(d_arena), nullptr, nullptr, stride, 0, count, 0};
     pa.sums = static_cast<uint16_t *>(d_out);
     pa.hi = (count - 1) * stride + len;
     pa.probe_form = 1;
@@ -196,21 +194,17 @@ int tcpck_probe_receive_ex(tcpck_ctx *ctx, int mode, void *d_arena, uint64_t str
   hipError_t e = ensure_side(ctx);
   if (e != hipSuccess) return hip_status(e);
   auto *arena = static_cast<uint8_t *>(d_arena);
+  const Images im = d_offsets ? Images::list(arena, d_offsets, d_lengths, 0, count, layout)
+                              : Images::fixed(arena, stride, len, count);
   tcpck::HeaderArgs h{};
-  h.arena = arena;
-  h.offsets = d_offsets;
-  h.stride = stride;
-  h.count = count;
+  h.im = im;
   h.out = static_cast<uint8_t *>(d_hdr);
   h.store_bits = hk.hdr_store_bits;
   e = hipEventRecord(ctx->fork, s);
   if (e == hipSuccess) e = hipStreamWaitEvent(ctx->side, ctx->fork, 0);
   if (e == hipSuccess) e = tcpck::launch_header_swap(h, static_cast<uint32_t>(ctx->num_cus), ctx->side);
   if (e == hipSuccess)
-    e = tcpck::api::run(ctx, TCPCK_OP_VERIFY, mode,
-                        d_offsets ? Images::list(arena, d_offsets, d_lengths, 0, count, layout)
-                                  : Images::fixed(arena, stride, len, count),
-                        d_ok, kernel, param, s, nullptr, hk);
+    e = tcpck::api::run(ctx, TCPCK_OP_VERIFY, mode, im, d_ok, kernel, param, s, nullptr, hk);
   const hipError_t e2 = hipEventRecord(ctx->join, ctx->side);
   const hipError_t e3 = e2 == hipSuccess ? hipStreamWaitEvent(s, ctx->join, 0) : e2;
   return hip_status(e != hipSuccess ? e : e3);

@@ -36,12 +36,12 @@ __device__ __forceinline__ uint16_t bswap16(uint16_t v) { return static_cast<uin
 template <bool FIXED, bool EXTRACT, bool WT = false>
 __global__ void __launch_bounds__(kBlock) header_swap_kernel(HeaderArgs a) {
   const uint64_t step = static_cast<uint64_t>(gridDim.x) * kBlock;
-  const uint64_t total = a.count * 8;
+  const uint64_t total = a.im.count * 8;
   for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; t < total; t += step) {
     const uint64_t k = t >> 3;
     const uint32_t j = static_cast<uint32_t>(t & 7);
-    const uint64_t start = FIXED ? k * a.stride : a.offsets[k];
-    uint16_t *w = reinterpret_cast<uint16_t *>(a.arena + start) + 2 * j;
+    const uint64_t start = a.im.start<FIXED>(k);
+    uint16_t *w = reinterpret_cast<uint16_t *>(a.im.arena + start) + 2 * j;
     const uint16_t lo = w[0], hi = w[1];
     if constexpr (EXTRACT) {
       // dense output: lane group k writes the 32 B of header k, whole lines
@@ -73,12 +73,12 @@ __global__ void __launch_bounds__(kBlock) header_swap_kernel(HeaderArgs a) {
 template <bool FIXED, int LP>
 __global__ void __launch_bounds__(kBlock) header_wide_kernel(HeaderArgs a) {
   const uint64_t step = static_cast<uint64_t>(gridDim.x) * kBlock;
-  const auto rsrc = dev::make_rsrc(a.arena, 0xFFFFFFF0u);
+  const auto rsrc = dev::make_rsrc(a.im.arena, 0xFFFFFFF0u);
   constexpr int aux = LP == 0 ? 0 : (LP == 1 ? 2 : (LP == 2 ? 17 : 16));
-  for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; t < a.count * 2; t += step) {
+  for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; t < a.im.count * 2; t += step) {
     const uint64_t k = t >> 1;
     const uint32_t h = static_cast<uint32_t>(t & 1);
-    const uint64_t start = FIXED ? k * a.stride : a.offsets[k];
+    const uint64_t start = a.im.start<FIXED>(k);
     typedef unsigned v4u __attribute__((ext_vector_type(4)));
     const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, static_cast<int>(start + 16 * h), 0, aux);
     const dev::u32x4 o{dev::n2h_dword(v.x, 0x00010203u), dev::n2h_dword(v.y, 0x00010203u),
@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(kBlock) header_wide_kernel(HeaderArgs a) {
 template <bool FIXED, int LP>
 hipError_t launch_wide(const HeaderArgs &a, uint32_t num_cus, hipStream_t s) {
   static const uint32_t per_cu = dev::resident_blocks_per_cu(header_wide_kernel<FIXED, LP>);
-  uint64_t blocks = (a.count * 2 + kBlock - 1) / kBlock;
+  uint64_t blocks = (a.im.count * 2 + kBlock - 1) / kBlock;
   const uint64_t cap = static_cast<uint64_t>(per_cu) * num_cus * 8;
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL((header_wide_kernel<FIXED, LP>), dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), 0, s, a);
@@ -129,17 +129,17 @@ __global__ void __launch_bounds__(kBlock) header_extract_kernel(HeaderArgs a) {
   uint32_t bid = blockIdx.x;
   if constexpr (ORDER == 1) bid = dev::ordered_block(blockIdx.x, gridDim.x, 4u);
   if constexpr (ORDER == 2) bid = static_cast<uint32_t>((uint64_t{blockIdx.x} * 2654435761ull) % gridDim.x);
-  const uint64_t n2 = a.count * 2;
+  const uint64_t n2 = a.im.count * 2;
   for (uint64_t t = static_cast<uint64_t>(bid) * kBlock + threadIdx.x; t < n2; t += step) {
     uint64_t k = t >> 1;
     const uint32_t h = static_cast<uint32_t>(t & 1);
     if constexpr (ORDER == 3) {
       // t's image as a 128 x (count / 128) transpose: lane pair i of block
       // group g reads image i * (count / 128) + g; the tail stays in order
-      const uint64_t rows = a.count >> 7, body = rows << 7;
+      const uint64_t rows = a.im.count >> 7, body = rows << 7;
       if (k < body) k = (k & 127u) * rows + (k >> 7);
     }
-    const uint8_t *p = a.arena + (FIXED ? k * a.stride : a.offsets[k]) + 16 * h;
+    const uint8_t *p = a.im.arena + a.im.start<FIXED>(k) + 16 * h;
     dev::u32x4 v;
     if ((reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
       v = *reinterpret_cast<const dev::u32x4 *>(p);
@@ -165,7 +165,7 @@ __global__ void __launch_bounds__(kBlock) header_extract_kernel(HeaderArgs a) {
 template <bool FIXED, int ORDER = 0>
 hipError_t launch_extract(const HeaderArgs &a, uint32_t num_cus, hipStream_t s) {
   static const uint32_t per_cu = dev::resident_blocks_per_cu(header_extract_kernel<FIXED, ORDER>);
-  uint64_t blocks = (a.count * 2 + kBlock - 1) / kBlock;
+  uint64_t blocks = (a.im.count * 2 + kBlock - 1) / kBlock;
   const uint64_t cap = static_cast<uint64_t>(per_cu) * num_cus * 8;
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL((header_extract_kernel<FIXED, ORDER>), dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), 0, s, a);
@@ -175,7 +175,7 @@ hipError_t launch_extract(const HeaderArgs &a, uint32_t num_cus, hipStream_t s) 
 template <bool FIXED, bool EXTRACT, bool WT = false>
 hipError_t launch_one(const HeaderArgs &a, uint32_t num_cus, hipStream_t s) {
   static const uint32_t per_cu = dev::resident_blocks_per_cu(header_swap_kernel<FIXED, EXTRACT, WT>);
-  uint64_t blocks = (a.count * 8 + kBlock - 1) / kBlock;
+  uint64_t blocks = (a.im.count * 8 + kBlock - 1) / kBlock;
   // grid-stride beyond 8 resident grids (4 loads in flight per lane measured no faster:
   // profiles/r02/receive_probe.log)
   const uint64_t cap = static_cast<uint64_t>(per_cu) * num_cus * 8;
@@ -209,29 +209,29 @@ __device__ __forceinline__ void store16_through(uint8_t *p, uint16_t c) {
 template <bool VAR, bool UPDATE>
 __global__ void __launch_bounds__(kBlock) patch_fields_kernel(PatchArgs a) {
   const uint64_t step = static_cast<uint64_t>(gridDim.x) * kBlock;
-  for (uint64_t kf = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; kf < a.count; kf += step) {
-    const uint64_t k = a.reverse ? a.count - 1 - kf : kf;
+  for (uint64_t kf = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; kf < a.im.count; kf += step) {
+    const uint64_t k = a.reverse ? a.im.count - 1 - kf : kf;
     uint64_t f;  // the field, relative to arena
     if constexpr (VAR) {
-      if (a.lengths[k] < 30) continue;  // no field
-      f = a.offsets[k] - a.base + 28;
+      if (a.im.length<false>(k) < 30) continue;  // no field
+      f = a.im.start<false>(k) + 28;
     } else {
-      f = k * a.stride + 28;
+      f = a.im.start<true>(k) + 28;
     }
     uint16_t c = a.sums[k];
     if constexpr (UPDATE) {
-      const uint16_t old = *reinterpret_cast<const uint16_t *>(a.arena + f);
+      const uint16_t old = *reinterpret_cast<const uint16_t *>(a.im.arena + f);
       c = static_cast<uint16_t>(~static_cast<uint16_t>(static_cast<uint16_t>(~c) - old));
       a.sums[k] = c;
     }
-    store16_through(a.arena + f, c);  // raw host order, tcp-header.h:177
+    store16_through(a.im.arena + f, c);  // raw host order, tcp-header.h:177
   }
 }
 
 template <bool VAR, bool UPDATE>
 hipError_t launch_patch(const PatchArgs &a, uint32_t num_cus, hipStream_t stream) {
   static const uint32_t per_cu = dev::resident_blocks_per_cu(patch_fields_kernel<VAR, UPDATE>);
-  uint64_t blocks = (a.count + kBlock - 1) / kBlock;
+  uint64_t blocks = (a.im.count + kBlock - 1) / kBlock;
   const uint64_t cap = static_cast<uint64_t>(per_cu) * num_cus * 8;
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL((patch_fields_kernel<VAR, UPDATE>), dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), 0, stream,
@@ -275,15 +275,15 @@ template <int G, bool BLIND, int BITS>
 __global__ void __launch_bounds__(kBlock) patch_probe_kernel(PatchArgs a) {
   constexpr int LPI = G == 3 ? 8 : (G == 0 ? 4 : (G == 4 ? 2 : 1));  // lanes per image
   const uint64_t step = static_cast<uint64_t>(gridDim.x) * kBlock;
-  const uint64_t total = a.count * LPI;
-  const uint64_t base = reinterpret_cast<uint64_t>(a.arena);
+  const uint64_t total = a.im.count * LPI;
+  const uint64_t base = reinterpret_cast<uint64_t>(a.im.arena);
   for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; t < total; t += step) {
     const uint64_t k = t / LPI;
     const uint32_t j = static_cast<uint32_t>(t % LPI);
-    const uint64_t f = k * a.stride + 28;
+    const uint64_t f = a.im.start<true>(k) + 28;
     const uint16_t c = a.sums[k];
     if constexpr (G == 2) {
-      uint16_t *p = reinterpret_cast<uint16_t *>(a.arena + f);
+      uint16_t *p = reinterpret_cast<uint16_t *>(a.im.arena + f);
       const uint32_t v = c;
       if constexpr (BITS == 7)
         asm volatile("global_store_short %0, %1, off sc0 sc1 nt" ::"v"(p), "v"(v) : "memory");
@@ -295,10 +295,10 @@ __global__ void __launch_bounds__(kBlock) patch_probe_kernel(PatchArgs a) {
       const uint64_t gm = G == 3 ? 127 : (G == 0 ? 63 : (G == 4 ? 31 : 15));
       const uint64_t blk = ((base + f) & ~gm) - base;
       if (G != 1 && (blk < a.lo || blk + gm + 1 > a.hi)) {  // the block would leave the batch
-        if (j == 0) *reinterpret_cast<uint16_t *>(a.arena + f) = c;
+        if (j == 0) *reinterpret_cast<uint16_t *>(a.im.arena + f) = c;
         continue;
       }
-      dev::u32x4 *p = reinterpret_cast<dev::u32x4 *>(a.arena + blk) + j;
+      dev::u32x4 *p = reinterpret_cast<dev::u32x4 *>(a.im.arena + blk) + j;
       dev::u32x4 v = BLIND ? dev::u32x4{0u, 0u, 0u, 0u} : *p;
       const uint32_t r = static_cast<uint32_t>(f - blk) - 16 * j;
       if (r < 16) {
@@ -324,19 +324,19 @@ __global__ void __launch_bounds__(kBlock) patch_map_kernel(PatchArgs a) {
   const uint64_t step = static_cast<uint64_t>(gridDim.x) * kBlock;
   const uint64_t t0 = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
   auto put = [&](uint64_t k) {
-    if (k < a.count) store16_through(a.arena + k * a.stride + 28, a.sums[k]);
+    if (k < a.im.count) store16_through(a.im.arena + a.im.start<true>(k) + 28, a.sums[k]);
   };
   if constexpr (MAP == 0) {
-    for (uint64_t t = t0; 4 * t < a.count; t += step)
+    for (uint64_t t = t0; 4 * t < a.im.count; t += step)
       for (int i = 0; i < 4; ++i) put(4 * t + i);
   } else if constexpr (MAP == 1) {
-    const uint64_t q = (a.count + 3) / 4;
+    const uint64_t q = (a.im.count + 3) / 4;
     for (uint64_t t = t0; t < q; t += step)
       for (int i = 0; i < 4; ++i) put(t + i * q);
   } else if constexpr (MAP == 2) {
-    for (uint64_t t = t0; t < a.count; t += step) put(t);
+    for (uint64_t t = t0; t < a.im.count; t += step) put(t);
   } else {
-    for (uint64_t b = static_cast<uint64_t>(blockIdx.x) * kBlock; b < a.count; b += step) {
+    for (uint64_t b = static_cast<uint64_t>(blockIdx.x) * kBlock; b < a.im.count; b += step) {
       const uint32_t x = threadIdx.x;
       put(b + (x & 31u) * 8u + (x >> 5));
     }
@@ -347,7 +347,7 @@ template <int G, bool BLIND, int BITS>
 hipError_t launch_patch_probe(const PatchArgs &a, uint32_t num_cus, hipStream_t stream) {
   static const uint32_t per_cu = dev::resident_blocks_per_cu(patch_probe_kernel<G, BLIND, BITS>);
   const uint64_t lpi = G == 3 ? 8 : (G == 0 ? 4 : (G == 4 ? 2 : 1));
-  uint64_t blocks = (a.count * lpi + kBlock - 1) / kBlock;
+  uint64_t blocks = (a.im.count * lpi + kBlock - 1) / kBlock;
   const uint64_t cap = static_cast<uint64_t>(per_cu) * num_cus * 8;
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL((patch_probe_kernel<G, BLIND, BITS>), dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), 0, stream,
@@ -376,15 +376,15 @@ hipError_t probe_by_bits(const PatchArgs &a, uint32_t num_cus, hipStream_t strea
 }  // namespace
 
 hipError_t launch_patch_fields(const PatchArgs &a, uint32_t num_cus, hipStream_t stream) {
-  if (a.count == 0) return hipSuccess;
+  if (a.im.count == 0) return hipSuccess;
   if (!a.sums) return hipErrorInvalidValue;
 #ifdef TCPCK_PROBE
   if (a.probe_form) {  // timing forms (TCPCK_KERNEL_PATCH param)
-    if (a.update || a.offsets) return hipErrorInvalidValue;
+    if (a.update || a.im.offsets) return hipErrorInvalidValue;
     if ((a.store_bits >> 4) >= 4 && (a.store_bits >> 4) < 8) {  // the 2-B write-through pass with other maps
       static const uint32_t per_cu = 8;
       const int map = static_cast<int>(a.store_bits >> 4) - 4;
-      uint64_t blocks = (a.count + kBlock - 1) / kBlock;
+      uint64_t blocks = (a.im.count + kBlock - 1) / kBlock;
       if (map == 0 || map == 1) blocks = (blocks + 3) / 4;
       if (map == 2) blocks = std::min<uint64_t>(blocks, static_cast<uint64_t>(per_cu) * num_cus);
       const dim3 g(static_cast<uint32_t>(blocks)), b(kBlock);
@@ -398,48 +398,48 @@ hipError_t launch_patch_fields(const PatchArgs &a, uint32_t num_cus, hipStream_t
       return hipGetLastError();
     }
     switch (a.store_bits >> 4) {
-      case 0: return a.stride >= 64 ? probe_by_bits<0>(a, num_cus, stream) : hipErrorInvalidValue;
+      case 0: return a.im.stride >= 64 ? probe_by_bits<0>(a, num_cus, stream) : hipErrorInvalidValue;
       case 1: return probe_by_bits<1>(a, num_cus, stream);
       case 2: return probe_by_bits<2>(a, num_cus, stream);
-      case 3: return a.stride >= 128 ? probe_by_bits<3>(a, num_cus, stream) : hipErrorInvalidValue;
-      case 8: return a.stride >= 64 ? probe_by_bits<0, true>(a, num_cus, stream) : hipErrorInvalidValue;
-      case 9: return a.stride >= 128 ? probe_by_bits<3, true>(a, num_cus, stream) : hipErrorInvalidValue;
+      case 3: return a.im.stride >= 128 ? probe_by_bits<3>(a, num_cus, stream) : hipErrorInvalidValue;
+      case 8: return a.im.stride >= 64 ? probe_by_bits<0, true>(a, num_cus, stream) : hipErrorInvalidValue;
+      case 9: return a.im.stride >= 128 ? probe_by_bits<3, true>(a, num_cus, stream) : hipErrorInvalidValue;
       case 10: return probe_by_bits<1, true>(a, num_cus, stream);
-      case 11: return a.stride >= 32 ? probe_by_bits<4, true>(a, num_cus, stream) : hipErrorInvalidValue;
-      case 12: return a.stride >= 32 ? probe_by_bits<4>(a, num_cus, stream) : hipErrorInvalidValue;
+      case 11: return a.im.stride >= 32 ? probe_by_bits<4, true>(a, num_cus, stream) : hipErrorInvalidValue;
+      case 12: return a.im.stride >= 32 ? probe_by_bits<4>(a, num_cus, stream) : hipErrorInvalidValue;
       default: return hipErrorInvalidValue;
     }
   }
 #endif
-  if (a.offsets) {
-    if (!a.lengths) return hipErrorInvalidValue;
+  if (a.im.offsets) {
+    if (!a.im.lengths) return hipErrorInvalidValue;
     return a.update ? launch_patch<true, true>(a, num_cus, stream) : launch_patch<true, false>(a, num_cus, stream);
   }
-  if (a.stride < 30) return hipErrorInvalidValue;  // every image holds a field
+  if (a.im.stride < 30) return hipErrorInvalidValue;  // every image holds a field
   return a.update ? launch_patch<false, true>(a, num_cus, stream) : launch_patch<false, false>(a, num_cus, stream);
 }
 
 hipError_t launch_header_swap(const HeaderArgs &a, uint32_t num_cus, hipStream_t stream) {
-  if (a.count == 0) return hipSuccess;
+  if (a.im.count == 0) return hipSuccess;
 #ifdef TCPCK_PROBE
   if (a.out && (a.store_bits & 2)) {  // the wide form: 16-B aligned images and array, arena < 4 GiB
-    if ((reinterpret_cast<uintptr_t>(a.arena) & 15u) || (reinterpret_cast<uintptr_t>(a.out) & 15u) ||
-        (!a.offsets && (a.stride & 15u)))
+    if ((reinterpret_cast<uintptr_t>(a.im.arena) & 15u) || (reinterpret_cast<uintptr_t>(a.out) & 15u) ||
+        (!a.im.offsets && (a.im.stride & 15u)))
       return hipErrorInvalidValue;
-    return a.offsets ? wide_by_policy<false>(a, num_cus, stream) : wide_by_policy<true>(a, num_cus, stream);
+    return a.im.offsets ? wide_by_policy<false>(a, num_cus, stream) : wide_by_policy<true>(a, num_cus, stream);
   }
   if (a.out && (a.store_bits >> 8) & 3u) {  // the array form in another image order
     switch ((a.store_bits >> 8) & 3u) {
-      case 1: return a.offsets ? launch_extract<false, 1>(a, num_cus, stream) : launch_extract<true, 1>(a, num_cus, stream);
-      case 2: return a.offsets ? launch_extract<false, 2>(a, num_cus, stream) : launch_extract<true, 2>(a, num_cus, stream);
-      default: return a.offsets ? launch_extract<false, 3>(a, num_cus, stream) : launch_extract<true, 3>(a, num_cus, stream);
+      case 1: return a.im.offsets ? launch_extract<false, 1>(a, num_cus, stream) : launch_extract<true, 1>(a, num_cus, stream);
+      case 2: return a.im.offsets ? launch_extract<false, 2>(a, num_cus, stream) : launch_extract<true, 2>(a, num_cus, stream);
+      default: return a.im.offsets ? launch_extract<false, 3>(a, num_cus, stream) : launch_extract<true, 3>(a, num_cus, stream);
     }
   }
   if (a.out && a.store_bits)
-    return a.offsets ? launch_one<false, true, true>(a, num_cus, stream) : launch_one<true, true, true>(a, num_cus, stream);
+    return a.im.offsets ? launch_one<false, true, true>(a, num_cus, stream) : launch_one<true, true, true>(a, num_cus, stream);
 #endif
-  if (a.out) return a.offsets ? launch_extract<false>(a, num_cus, stream) : launch_extract<true>(a, num_cus, stream);
-  return a.offsets ? launch_one<false, false>(a, num_cus, stream) : launch_one<true, false>(a, num_cus, stream);
+  if (a.out) return a.im.offsets ? launch_extract<false>(a, num_cus, stream) : launch_extract<true>(a, num_cus, stream);
+  return a.im.offsets ? launch_one<false, false>(a, num_cus, stream) : launch_one<true, false>(a, num_cus, stream);
 }
 
 #ifdef TCPCK_PROBE

@@ -1,5 +1,9 @@
 // tcpck_internal.h -- private interface between the C-ABI layer (tcpck_api.hip,
-// tcpck_router.hip) and the gfx950 kernels (tcpck_kernels.hip, tcpck_rstream.hip, tcpck_vvstream.hip).
+// tcpck_router.hip and the other entry points) and the gfx950 kernels: one
+// launcher and one argument struct per kernel file.  Where a batch's images
+// are is one value, ImageSpan, which every launcher that addresses images by
+// index holds as `im` beside its own fields; the streams that take packed
+// fixed images or a pre-digested form (rstream, gstream, segment) keep theirs.
 // Not installed.
 #pragma once
 
@@ -13,17 +17,45 @@ namespace tcpck {
 enum Op : int { kChecksum = 0, kFill = 1, kVerify = 2 };
 enum Mode : int { kRef = 0, kRfc1071 = 1 };
 
+// ---- where a batch's images are, and the rule that reads it ----
+// `count` images of `len` bytes every `stride` bytes from `arena` (the fixed
+// layout: offsets and lengths null, base 0), or image k at arena + offsets[k]
+// - base with lengths[k] bytes (an offset list: stride and len 0).
+struct ImageSpan {
+  uint8_t *arena;            // image bytes (device)
+  const uint64_t *offsets;   // variable layout: byte offset of image k (device); null: fixed layout
+  const uint32_t *lengths;   // variable layout: byte length of image k (device)
+  uint64_t stride;           // fixed layout: image k at k * stride
+  uint64_t base;             // subtracted from offsets[k] (chunked host batches)
+  uint64_t count;            // images
+  uint32_t len;              // fixed layout: image length (<= stride)
+
+  __host__ __device__ bool is_fixed() const { return !offsets; }
+  // Image k's first byte, relative to arena, and its length.  FIXED is the
+  // kernels' template parameter; the run-time forms branch on `offsets`.
+  template <bool FIXED>
+  __host__ __device__ __forceinline__ uint64_t start(uint64_t k) const {
+    if constexpr (FIXED) return k * stride;
+    else return offsets[k] - base;
+  }
+  template <bool FIXED>
+  __host__ __device__ __forceinline__ uint32_t length(uint64_t k) const {
+    if constexpr (FIXED) return len;
+    else return lengths[k];
+  }
+  __host__ __device__ __forceinline__ uint64_t start(uint64_t k) const {
+    return offsets ? start<false>(k) : start<true>(k);
+  }
+  __host__ __device__ __forceinline__ uint32_t length(uint64_t k) const {
+    return offsets ? length<false>(k) : length<true>(k);
+  }
+};
+
 // ---- seg kernel: any layout, G lanes per image, U loads of 16 B in flight
 // (SegShape and shape_for_len: tcpck_plan.h) ----
 struct SegArgs {
-  uint8_t *arena;            // image bytes (device)
-  const uint64_t *offsets;   // variable layout: byte offset of image k (device)
-  const uint32_t *lengths;   // variable layout: byte length of image k (device)
-  uint64_t stride;           // fixed layout: image k at k*stride
-  uint64_t base;             // subtracted from offsets[k] (chunked host batches)
-  uint64_t count;            // images
+  ImageSpan im;
   void *out;                 // u16[count] or u8[count] (verify); may be null for fill
-  uint32_t len;              // fixed layout: image length
   uint32_t oversub;          // grid = resident blocks x this (0/1: one block per resident slot)
   uint32_t order;            // block order (dev::ordered_block; 0xFF default)
   uint32_t rot;              // W-wave shapes: image k's chunks read from chunk ((k rot) mod (n / 64)) 64 on,
@@ -36,13 +68,7 @@ hipError_t launch_seg(int op, int mode, bool fixed, SegShape shape, const SegArg
 // ---- run kernels: one contiguous run of whole images per wave ---------------
 // Packed and fixed layouts for vvstream (tcpck_vvstream.hip).
 struct RunArgs {
-  uint8_t *arena;
-  const uint64_t *offsets;   // variable layout (packed: offsets[k+1] == offsets[k] + lengths[k])
-  const uint32_t *lengths;
-  uint64_t stride;           // fixed layouts: image k at k * stride
-  uint32_t len;              // fixed layouts: image length (<= stride)
-  uint64_t base;             // subtracted from offsets[k] (chunked host batches)
-  uint64_t count;
+  ImageSpan im;              // (packed offset lists: offsets[k+1] == offsets[k] + lengths[k])
   void *out;
   uint32_t oversub;          // grid = resident blocks x this (0 = by size)
   uint64_t total_bytes;      // batch byte span hint (0 = unknown)
@@ -99,7 +125,7 @@ hipError_t launch_gstream(int op, int variant, const GroupStreamArgs &a, uint32_
 // 4-8 issue-priority experiments, 9-13 v_dot2 sums and/or buffer loads (10 = policy)
 hipError_t launch_rstream(int op, int variant, const FixedStreamArgs &a, uint32_t num_cus, hipStream_t stream);
 // ---- vvstream (prefix table), MODE_REF, all ops: packed variable layouts
-// (fixed = false) or fixed strides (fixed = true: a.stride >= a.len).
+// (fixed = false) or fixed strides (fixed = true: a.im.stride >= a.im.len).
 // variant 0 U4 byte split, 1 U8, 2 U4 count split, 3 U8 (fixed: 0/2 U4, 1/3 U8),
 // 4 = policy (oversubscription, split and loads in flight by size)
 hipError_t launch_vvstream(int op, int variant, bool fixed, const RunArgs &a, uint32_t num_cus, hipStream_t stream);
@@ -134,20 +160,14 @@ struct SegmentArgs {
 hipError_t launch_segment(int mode, int variant, SegmentArgs a, uint32_t oversub, uint32_t num_cus,
                           hipStream_t stream);
 // ---- deliver (tcpck_deliver.hip): accepted payloads -> the receive stream ----
-// Image k at k * stride, `len` bytes (offsets == null) or at offsets[k],
-// lengths[k] bytes; its payload (bytes 32..) goes to recv[dst[k], ...) unless
-// dst[k] is TCPCK_DELIVER_SKIP, odd, or the range does not fit recv_bytes.
+// Image k's payload (bytes 32..) goes to recv[dst[k], ...) unless dst[k] is
+// TCPCK_DELIVER_SKIP, odd, or the range does not fit recv_bytes.
 struct DeliverArgs {
-  const uint8_t *arena;      // even
-  const uint64_t *offsets;   // null: fixed stride
-  const uint32_t *lengths;
+  ImageSpan im;              // arena even and only read; base 0
   const uint64_t *dst;       // u64[count]
   uint8_t *recv;             // 16-B aligned
-  uint64_t stride;
-  uint64_t count;
   uint64_t recv_bytes;
   uint64_t per_block, rem;   // run split over the blocks, set by the launcher
-  uint32_t len;
   uint32_t order;            // block order, set by the launcher
 };
 // run > 0 replaces the launcher's images-per-block rule, max_blocks > 0 its cap
@@ -158,10 +178,7 @@ hipError_t launch_deliver(DeliverArgs a, uint32_t num_cus, uint64_t run, uint64_
 
 // ---- retransmit ACK rewrite with incremental checksum update (tcpck_resend.hip) ----
 struct AckArgs {
-  uint8_t *arena;
-  const uint64_t *offsets;  // null: image k at k * stride
-  uint64_t stride;
-  uint64_t count;
+  ImageSpan im;             // lengths unused, base 0
   const uint32_t *acks;     // per-image ACK numbers (host order); null: `ack` for all
   uint32_t ack;
   uint16_t *out;            // new checksums (may be null)
@@ -170,10 +187,7 @@ hipError_t launch_set_ack(int mode, const AckArgs &a, uint32_t num_cus, hipStrea
 
 // ---- header byte-order conversion, TcpHeaderN2H == TcpHeaderH2N (tcpck_header.hip) ----
 struct HeaderArgs {
-  uint8_t *arena;
-  const uint64_t *offsets;  // null: image k at k * stride
-  uint64_t stride;
-  uint64_t count;
+  ImageSpan im;             // lengths unused
   uint8_t *out;             // null: convert in place; else header k -> out[32k, 32k + 32), arena untouched
   uint32_t store_bits;      // probe builds (tcpck_probe_receive_ex), EXTRACT: 1 = write-through
                             // (sc0 sc1 nt) array stores; 2 = two lanes per image, 16-B loads with
@@ -193,12 +207,7 @@ hipError_t launch_header_swap(const HeaderArgs &a, uint32_t num_cus, hipStream_t
 // mod 2^16); c goes to the field and back to sums[k].  Images < 30 B keep
 // their plain checksum and are not written (seg's FILL does the same).
 struct PatchArgs {
-  uint8_t *arena;
-  uint64_t stride;          // image k at k * stride
-  const uint64_t *offsets;  // or image k at offsets[k] - base, lengths[k] bytes
-  const uint32_t *lengths;
-  uint64_t base;
-  uint64_t count;
+  ImageSpan im;
   uint16_t *sums;
   uint64_t lo, hi;          // probe block forms: byte range (relative to arena) their writes may cover
   uint32_t update;          // 1: sums hold CHECKSUM results, derive FILL's from the old field

@@ -41,12 +41,12 @@ __global__ void __launch_bounds__(kBlock) seg_kernel(SegArgs a) {
   const uint32_t gl = threadIdx.x & (G - 1);
   const uint64_t groups_per_grid = static_cast<uint64_t>(gridDim.x) * (kBlock / G);
   const uint32_t bid = dev::ordered_block(blockIdx.x, gridDim.x, a.order);
-  for (uint64_t k = (static_cast<uint64_t>(bid) * kBlock + threadIdx.x) / G; k < a.count;
+  for (uint64_t k = (static_cast<uint64_t>(bid) * kBlock + threadIdx.x) / G; k < a.im.count;
        k += groups_per_grid) {
-    const uint64_t start = FIXED ? k * a.stride : a.offsets[k] - a.base;
-    const uint32_t len = FIXED ? a.len : a.lengths[k];
-    const uint64_t a0 = dev::align16_rel(a.arena, start);     // 16-B aligned in absolute terms
-    const uint8_t *p0 = a.arena + a0;
+    const uint64_t start = a.im.start<FIXED>(k);
+    const uint32_t len = a.im.length<FIXED>(k);
+    const uint64_t a0 = dev::align16_rel(a.im.arena, start);     // 16-B aligned in absolute terms
+    const uint8_t *p0 = a.im.arena + a0;
     const int64_t lead = static_cast<int64_t>(start - a0);    // masked bytes before the image
     const int64_t span = lead + static_cast<int64_t>(len);    // bytes from p0 to the image end
     const uint32_t nch = static_cast<uint32_t>((span + 15) >> 4);  // 16-byte chunks touched
@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(kBlock) seg_kernel(SegArgs a) {
       } else {
         if (a.out) static_cast<uint16_t *>(a.out)[k] = c;
         if (OP == kFill && len >= 30)
-          *reinterpret_cast<uint16_t *>(a.arena + start + 28) = c;  // stored raw, tcp-header.h:177
+          *reinterpret_cast<uint16_t *>(a.im.arena + start + 28) = c;  // stored raw, tcp-header.h:177
       }
     }
   }
@@ -105,11 +105,11 @@ __global__ void __launch_bounds__(64 * W) jumbo_kernel(SegArgs a) {
   __shared__ uint32_t s_part[W];
   const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const uint32_t bid = dev::ordered_block(blockIdx.x, gridDim.x, a.order);
-  for (uint64_t k = bid; k < a.count; k += gridDim.x) {
-    const uint64_t start = FIXED ? k * a.stride : a.offsets[k] - a.base;
-    const uint32_t len = FIXED ? a.len : a.lengths[k];
-    const uint64_t a0 = dev::align16_rel(a.arena, start);
-    const uint8_t *p0 = a.arena + a0;
+  for (uint64_t k = bid; k < a.im.count; k += gridDim.x) {
+    const uint64_t start = a.im.start<FIXED>(k);
+    const uint32_t len = a.im.length<FIXED>(k);
+    const uint64_t a0 = dev::align16_rel(a.im.arena, start);
+    const uint8_t *p0 = a.im.arena + a0;
     const int64_t lead = static_cast<int64_t>(start - a0);
     const int64_t span = lead + static_cast<int64_t>(len);
     const uint32_t nch = static_cast<uint32_t>((span + 15) >> 4);
@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(64 * W) jumbo_kernel(SegArgs a) {
         static_cast<uint8_t *>(a.out)[k] = (c == 0) ? 1 : 0;
       } else {
         if (a.out) static_cast<uint16_t *>(a.out)[k] = c;
-        if (OP == kFill && len >= 30) *reinterpret_cast<uint16_t *>(a.arena + start + 28) = c;
+        if (OP == kFill && len >= 30) *reinterpret_cast<uint16_t *>(a.im.arena + start + 28) = c;
       }
     }
     __syncthreads();  // s_part is rewritten for the next image
@@ -179,7 +179,7 @@ hipError_t launch_jumbo(const SegArgs &a, uint32_t num_cus, hipStream_t stream) 
     return static_cast<uint32_t>(nb);
   }();
   // one image per block (oversub 0) or at most oversub x the resident blocks (grid-stride)
-  uint64_t blocks = a.count;
+  uint64_t blocks = a.im.count;
   const uint64_t cap = a.oversub ? static_cast<uint64_t>(per_cu) * num_cus * a.oversub : uint64_t{0x7FFFFFFF};
   if (blocks > cap) blocks = cap;
   if (blocks == 0) return hipSuccess;
@@ -191,7 +191,7 @@ hipError_t launch_jumbo(const SegArgs &a, uint32_t num_cus, hipStream_t stream) 
 template <int G, int U, int MODE, int OP, bool FIXED>
 hipError_t launch_one(const SegArgs &a, uint32_t num_cus, hipStream_t stream) {
   const uint64_t groups_per_block = kBlock / G;
-  uint64_t blocks = (a.count + groups_per_block - 1) / groups_per_block;
+  uint64_t blocks = (a.im.count + groups_per_block - 1) / groups_per_block;
   // grid-stride kernel: launch exactly the resident blocks, never a second wave of them
   static const uint32_t per_cu = dev::resident_blocks_per_cu(seg_kernel<G, U, MODE, OP, FIXED>);
   const uint64_t max_blocks = static_cast<uint64_t>(per_cu) * num_cus * (a.oversub > 1 ? a.oversub : 1u);

@@ -30,9 +30,9 @@ using dev::update_ack;  // (shared with tcpck_resend_queue.hip)
 template <int MODE, bool FIXED, bool PER_IMAGE>
 __global__ void __launch_bounds__(kBlock) set_ack_kernel(AckArgs a) {
   const uint64_t step = static_cast<uint64_t>(gridDim.x) * kBlock;
-  for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; k < a.count; k += step) {
-    const uint64_t start = FIXED ? k * a.stride : a.offsets[k];
-    uint16_t *w = reinterpret_cast<uint16_t *>(a.arena + start);  // even offsets: u16-aligned
+  for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; k < a.im.count; k += step) {
+    const uint64_t start = a.im.start<FIXED>(k);
+    uint16_t *w = reinterpret_cast<uint16_t *>(a.im.arena + start);  // even offsets: u16-aligned
     const uint16_t o0 = w[10], o1 = w[11], c = w[14];
     // htonl(ack) stored raw: memory bytes 20..23 = ack >> 24, >> 16, >> 8, ack
     const uint32_t net = __builtin_bswap32(PER_IMAGE ? a.acks[k] : a.ack);
@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(kBlock) set_ack_kernel(AckArgs a) {
 template <int MODE, bool FIXED, bool PER_IMAGE>
 hipError_t launch_one(const AckArgs &a, uint32_t num_cus, hipStream_t s) {
   static const uint32_t per_cu = dev::resident_blocks_per_cu(set_ack_kernel<MODE, FIXED, PER_IMAGE>);
-  uint64_t blocks = (a.count + kBlock - 1) / kBlock;
+  uint64_t blocks = (a.im.count + kBlock - 1) / kBlock;
   const uint64_t cap = static_cast<uint64_t>(per_cu) * num_cus * 8;  // grid-stride beyond 8 resident grids
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL((set_ack_kernel<MODE, FIXED, PER_IMAGE>), dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), 0,
@@ -58,7 +58,7 @@ hipError_t launch_one(const AckArgs &a, uint32_t num_cus, hipStream_t s) {
 
 template <int MODE>
 hipError_t dispatch(const AckArgs &a, uint32_t num_cus, hipStream_t s) {
-  const bool fixed = a.offsets == nullptr, per = a.acks != nullptr;
+  const bool fixed = a.im.is_fixed(), per = a.acks != nullptr;
   if (fixed) return per ? launch_one<MODE, true, true>(a, num_cus, s) : launch_one<MODE, true, false>(a, num_cus, s);
   return per ? launch_one<MODE, false, true>(a, num_cus, s) : launch_one<MODE, false, false>(a, num_cus, s);
 }
@@ -66,7 +66,7 @@ hipError_t dispatch(const AckArgs &a, uint32_t num_cus, hipStream_t s) {
 }  // namespace
 
 hipError_t launch_set_ack(int mode, const AckArgs &a, uint32_t num_cus, hipStream_t stream) {
-  if (a.count == 0) return hipSuccess;
+  if (a.im.count == 0) return hipSuccess;
   return mode == kRef ? dispatch<kRef>(a, num_cus, stream) : dispatch<kRfc1071>(a, num_cus, stream);
 }
 

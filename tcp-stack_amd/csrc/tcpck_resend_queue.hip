@@ -45,28 +45,25 @@ using compact::kChunks;
 using dev::u32x4;
 
 struct MarkArgs {
-  uint8_t *arena;
+  ImageSpan im;          // base 0
   uint64_t arena_bytes;
-  uint64_t stride, fit;  // fixed form: image k fits the arena iff k < fit (resend::fit_count)
-  const uint64_t *offsets;
-  const uint32_t *lengths;
+  uint64_t fit;          // fixed form: image k fits the arena iff k < fit (resend::fit_count)
   const uint32_t *conn;
   const tcpck_snd_state *snd;
   uint8_t *keep_out;     // d_keep, may be NULL
   uint8_t *keep;         // the scratch's keep bytes
   uint32_t *totals;      // the scratch's block totals
-  uint32_t len, n_conns, count;
+  uint32_t n_conns;
 };
 
 // Image k of the queue: whether its bytes may be touched at all, and where they are.
 template <bool FIXED>
 __device__ __forceinline__ bool image_at(const MarkArgs &a, uint32_t k, uint64_t &off) {
+  off = a.im.start<FIXED>(k);  // (fixed form: used only when k < fit: no overflow then)
   if constexpr (FIXED) {
-    off = static_cast<uint64_t>(k) * a.stride;  // (used only when k < fit: no overflow then)
     return k < a.fit;
   } else {
-    off = a.offsets[k];
-    const uint32_t ln = a.lengths[k];
+    const uint32_t ln = a.im.length<FIXED>(k);
     return !((off | ln) & 1u) && ln >= resend::kMinImage && off <= a.arena_bytes && ln <= a.arena_bytes - off;
   }
 }
@@ -80,14 +77,14 @@ __global__ void __launch_bounds__(compact::kBlock) resend_mark_kernel(MarkArgs a
   for (uint32_t i = 0; i < kChunks; ++i) {
     const uint32_t k = first + 64u * i;
     bool keep = false;
-    if (k < a.count) {
+    if (k < a.im.count) {
       uint64_t off;
       const bool fits = image_at<FIXED>(a, k, off);
       const uint32_t c = a.conn ? a.conn[k] : 0u;
       if (fits && c < a.n_conns) {  // (TCPCK_CONN_NONE is >= every n_conns: the dead weak_ptr)
         const u32x4 st = *reinterpret_cast<const u32x4 *>(a.snd + c);  // snd_una, rcv_nxt, flags, reserved
         if (!(st.z & TCPCK_SND_CLOSED)) {
-          uint16_t *w = reinterpret_cast<uint16_t *>(a.arena + off);  // even offsets: u16-aligned
+          uint16_t *w = reinterpret_cast<uint16_t *>(a.im.arena + off);  // even offsets: u16-aligned
           const uint32_t seq =
               __builtin_bswap32(w[resend::kWordSeq] | static_cast<uint32_t>(w[resend::kWordSeq + 1]) << 16);
           const uint32_t edge = ((w[resend::kWordFlags] >> 8) & resend::kSynFin) ? 1u : 0u;
@@ -116,16 +113,13 @@ __global__ void __launch_bounds__(compact::kBlock) resend_mark_kernel(MarkArgs a
 }
 
 struct EmitArgs {
+  ImageSpan im;             // arena unused, base 0
   const uint8_t *keep;
   const uint32_t *block_offsets;
-  uint64_t stride;
-  const uint64_t *offsets;  // NULL: the fixed form (k * stride, len)
-  const uint32_t *lengths;
   const uint32_t *conn;
   uint64_t *out_offsets;
   uint32_t *out_lengths, *out_conn, *src;
   uint64_t out_cap;
-  uint32_t len, count;
 };
 
 __global__ void __launch_bounds__(compact::kBlock) resend_emit_kernel(EmitArgs a) {
@@ -137,7 +131,7 @@ __global__ void __launch_bounds__(compact::kBlock) resend_emit_kernel(EmitArgs a
 #pragma unroll
   for (uint32_t i = 0; i < kChunks; ++i) {
     const uint32_t k = first + 64u * i;
-    keep[i] = k < a.count && a.keep[k] != 0;
+    keep[i] = k < a.im.count && a.keep[k] != 0;
     ballot[i] = __ballot(keep[i]);
     n += __popcll(ballot[i]);
   }
@@ -148,8 +142,8 @@ __global__ void __launch_bounds__(compact::kBlock) resend_emit_kernel(EmitArgs a
     const uint32_t j = at + compact::lanes_below(ballot[i]);
     at += __popcll(ballot[i]);
     if (!keep[i] || j >= a.out_cap) continue;
-    if (a.out_offsets) a.out_offsets[j] = a.offsets ? a.offsets[k] : static_cast<uint64_t>(k) * a.stride;
-    if (a.out_lengths) a.out_lengths[j] = a.lengths ? a.lengths[k] : a.len;
+    if (a.out_offsets) a.out_offsets[j] = a.im.start(k);
+    if (a.out_lengths) a.out_lengths[j] = a.im.length(k);
     if (a.out_conn) a.out_conn[j] = a.conn ? a.conn[k] : 0u;
     if (a.src) a.src[j] = k;
   }
@@ -157,7 +151,7 @@ __global__ void __launch_bounds__(compact::kBlock) resend_emit_kernel(EmitArgs a
 
 template <int MODE, int RULE>
 void launch_mark(const MarkArgs &a, uint32_t blocks, hipStream_t stream) {
-  if (a.offsets) {
+  if (!a.im.is_fixed()) {
     hipLaunchKernelGGL((resend_mark_kernel<MODE, RULE, false>), dim3(blocks), dim3(compact::kBlock), 0, stream, a);
   } else {
     hipLaunchKernelGGL((resend_mark_kernel<MODE, RULE, true>), dim3(blocks), dim3(compact::kBlock), 0, stream, a);
@@ -170,7 +164,7 @@ void launch_mark(const MarkArgs &a, uint32_t blocks, hipStream_t stream) {
 static hipError_t launch_resend(int mode, int rule, MarkArgs m, EmitArgs e, uint64_t *d_count, hipStream_t stream) {
   // one launch covers every queue the entry point accepts: 2^31 images are 2^21
   // blocks, and every image and survivor index fits in a u32
-  const uint32_t blocks = static_cast<uint32_t>(reply::blocks_for(m.count));
+  const uint32_t blocks = static_cast<uint32_t>(reply::blocks_for(m.im.count));
   if (mode == TCPCK_MODE_REF) {
     rule == TCPCK_RESEND_REF ? launch_mark<kRef, TCPCK_RESEND_REF>(m, blocks, stream)
                              : launch_mark<kRef, TCPCK_RESEND_SERIAL>(m, blocks, stream);
@@ -217,35 +211,25 @@ extern "C" int tcpck_batch_resend(tcpck_ctx *ctx, int mode, int rule, void *d_ar
   uint8_t *scratch = static_cast<uint8_t *>(d_scratch);
   uint32_t *totals = reinterpret_cast<uint32_t *>(scratch);
   uint8_t *keep = scratch + tcpck::resend::totals_bytes(count);
-  const uint32_t n = static_cast<uint32_t>(count);
   tcpck::MarkArgs m{};
-  m.arena = static_cast<uint8_t *>(d_arena);
+  m.im = {static_cast<uint8_t *>(d_arena), d_offsets, d_lengths, stride, 0, count, len};
   m.arena_bytes = arena_bytes;
-  m.stride = stride;
   m.fit = d_offsets ? 0 : tcpck::resend::fit_count(arena_bytes, stride, len);
-  m.offsets = d_offsets;
-  m.lengths = d_lengths;
   m.conn = d_conn;
   m.snd = d_snd;
   m.keep_out = d_keep;
   m.keep = keep;
   m.totals = totals;
-  m.len = len;
   m.n_conns = n_conns;
-  m.count = n;
   tcpck::EmitArgs e{};
+  e.im = m.im;
   e.keep = keep;
   e.block_offsets = totals;
-  e.stride = stride;
-  e.offsets = d_offsets;
-  e.lengths = d_lengths;
   e.conn = d_conn;
   e.out_offsets = d_out_offsets;
   e.out_lengths = d_out_lengths;
   e.out_conn = d_out_conn;
   e.src = d_src;
   e.out_cap = out_cap;
-  e.len = len;
-  e.count = n;
   return hip_status(tcpck::launch_resend(mode, rule, m, e, d_count, s));
 }

@@ -6,8 +6,9 @@
 // a plan on the caller's buffers and decide nothing.  The images of a batch are
 // one value, Images (tcpck_api_internal.h), whichever layout they have, so
 // the launcher, the FILL front (scratch slots, the pipelined form) and the
-// validated entry points exist once.  tests/cpp/router_trace.cc records every
-// launch of this file without a GPU.
+// validated entry points exist once; its ImageSpan (tcpck_internal.h) is what
+// every launcher's argument struct takes, assigned whole.
+// tests/cpp/router_trace.cc records every launch of this file without a GPU.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,9 +48,9 @@ hipError_t launch_patch_on(const tcpck::PatchArgs &pa, uint32_t num_cus, hipStre
 }
 
 // A plan's stream kernel on the batch.  Each launcher's argument struct gets
-// the fields of the batch's layout and zeros for the other layout's (Images
-// holds them so); rstream and gstream take fixed layouts only, rvstream offset
-// lists only (the plans reject the rest).
+// the batch's span (the fields of its layout and zeros for the other layout's);
+// rstream and gstream take fixed layouts only, rvstream offset lists only (the
+// plans reject the rest).
 hipError_t launch_stream(tcpck_ctx *ctx, const Plan &p, int mode, const Images &im, void *out, uint8_t *hdr,
                          hipStream_t s) {
   const auto num_cus = static_cast<uint32_t>(ctx->num_cus);
@@ -83,13 +84,7 @@ hipError_t launch_stream(tcpck_ctx *ctx, const Plan &p, int mode, const Images &
     }
     case TCPCK_KERNEL_SEG: {
       tcpck::SegArgs a{};
-      a.arena = im.arena;
-      a.offsets = im.offsets;
-      a.lengths = im.lengths;
-      a.stride = im.stride;
-      a.len = im.len;
-      a.base = im.base;
-      a.count = im.count;
+      a.im = im;
       a.out = out;
       a.oversub = oversub;
       a.order = ((param >> 24) & 1u) ? 4u : 0xFFu;  // bit 24: XCD-chunked order, groups of 16 blocks
@@ -101,19 +96,13 @@ hipError_t launch_stream(tcpck_ctx *ctx, const Plan &p, int mode, const Images &
     case TCPCK_KERNEL_VVSTREAM: {
       tcpck::RunArgs a{};
       a.mode = mode == TCPCK_MODE_REF ? tcpck::kRef : tcpck::kRfc1071;
-      a.arena = im.arena;
-      a.offsets = im.offsets;
-      a.lengths = im.lengths;
-      a.stride = im.stride;
-      a.len = im.len;
-      a.base = im.base;
-      a.count = im.count;
+      a.im = im;
       a.out = out;
       a.oversub = oversub;
       a.total_bytes = im.total_bytes;
       if (p.kernel == TCPCK_KERNEL_RVSTREAM) return tcpck::launch_rvstream(p.op, param & 0xFF, a, num_cus, s);
       if (p.kernel == TCPCK_KERNEL_SSTREAM) {
-        if (fixed && im.count == 1) a.stride = (static_cast<uint64_t>(im.len) + 15) & ~uint64_t{15};  // one image: never read
+        if (fixed && im.count == 1) a.im.stride = (static_cast<uint64_t>(im.len) + 15) & ~uint64_t{15};  // one image: never read
         if (p.hdr == Hdr::kFused) a.hdr = hdr;
         return tcpck::launch_sstream(p.op, param & 0xFF, fixed, a, num_cus, s);
       }
@@ -134,10 +123,7 @@ hipError_t launch(tcpck_ctx *ctx, const Plan &p, int mode, const Images &im, voi
   const auto num_cus = static_cast<uint32_t>(ctx->num_cus);
   auto header_pass = [&]() {
     tcpck::HeaderArgs h{};
-    h.arena = im.arena;
-    h.offsets = im.offsets;
-    h.stride = im.stride;
-    h.count = im.count;
+    h.im = im;
     h.out = hdr;
     h.store_bits = hk.hdr_store_bits;
     return tcpck::launch_header_swap(h, num_cus, s);
@@ -147,12 +133,7 @@ hipError_t launch(tcpck_ctx *ctx, const Plan &p, int mode, const Images &im, voi
   if (e != hipSuccess) return e;
   if (p.field_pass()) {  // the fields the stream left: write-through 2-B stores (launch_patch_fields)
     tcpck::PatchArgs pa{};
-    pa.arena = im.arena;
-    pa.offsets = im.offsets;
-    pa.lengths = im.lengths;
-    pa.stride = im.stride;
-    pa.base = im.base;
-    pa.count = im.count;
+    pa.im = im;
     pa.sums = static_cast<uint16_t *>(out);
     if (im.is_fixed())
       pa.hi = (im.count - 1) * im.stride + im.len;  // (lo = 0)

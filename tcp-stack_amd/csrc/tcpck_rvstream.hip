@@ -207,12 +207,13 @@ __global__ void __launch_bounds__(kBlock) rvstream_kernel(RVArgs a) {
 }
 
 template <int U, int OP>
-hipError_t launch_one(const RunArgs &s, uint32_t num_cus, hipStream_t stream, bool table = false) {
+hipError_t launch_one(const RunArgs &r, uint32_t num_cus, hipStream_t stream, bool table = false) {
+  const ImageSpan &s = r.im;
   static const uint32_t per_cu = dev::resident_blocks_per_cu(rvstream_kernel<U, OP>);
   const uint64_t resident = static_cast<uint64_t>(per_cu) * num_cus;
   // M x the resident grid as rstream: the largest power of two keeping runs >= 4 KiB
-  const uint64_t bytes = s.total_bytes ? s.total_bytes : s.count * 1024;
-  uint64_t blocks = resident * dev::oversub_for(s.oversub, bytes, resident * kWavesPerBlock, 1024);
+  const uint64_t bytes = r.total_bytes ? r.total_bytes : s.count * 1024;
+  uint64_t blocks = resident * dev::oversub_for(r.oversub, bytes, resident * kWavesPerBlock, 1024);
   const uint64_t need = (s.count + kWavesPerBlock - 1) / kWavesPerBlock;  // >= 1 image per wave
   if (blocks > need) blocks = need;
   if (blocks == 0) return hipSuccess;
@@ -222,7 +223,7 @@ hipError_t launch_one(const RunArgs &s, uint32_t num_cus, hipStream_t stream, bo
   a.lengths = s.lengths;
   a.base = s.base;
   a.count = s.count;
-  a.out = s.out;
+  a.out = r.out;
   a.per_wave = s.count / (blocks * kWavesPerBlock);
   a.rem = s.count % (blocks * kWavesPerBlock);
   a.order = 4u;  // XCD-chunked: groups of 16 blocks per XCD
@@ -268,7 +269,7 @@ hipError_t launch_one(const RunArgs &s, uint32_t num_cus, hipStream_t stream, bo
 // param >> 16 = M).  The product library refuses it.
 hipError_t launch_rvstream(int op, int variant, const RunArgs &a, uint32_t num_cus, hipStream_t stream) {
 #ifdef TCPCK_PROBE
-  if (a.count == 0) return hipSuccess;
+  if (a.im.count == 0) return hipSuccess;
   if (a.mode != kRef || !a.out || (op != kChecksum && op != kVerify)) return hipErrorInvalidValue;
   if (variant == 0)
     return op == kVerify ? launch_one<4, kVerify>(a, num_cus, stream) : launch_one<4, kChecksum>(a, num_cus, stream);

@@ -619,13 +619,14 @@ hipError_t dispatch(int op, const SSArgs &a, uint32_t m, uint64_t min_waves, uin
 }  // namespace
 
 hipError_t launch_sstream(int op, int variant, bool fixed, const RunArgs &r, uint32_t num_cus, hipStream_t stream) {
-  if (r.count == 0) return hipSuccess;
+  const ImageSpan &im = r.im;
+  if (im.count == 0) return hipSuccess;
   SSArgs a{};
-  a.arena = r.arena;
-  a.offsets = r.offsets;
-  a.lengths = r.lengths;
-  a.base = r.base;
-  a.count = r.count;
+  a.arena = im.arena;
+  a.offsets = im.offsets;
+  a.lengths = im.lengths;
+  a.base = im.base;
+  a.count = im.count;
   a.out = r.out;
   a.mode = r.mode;
   a.hdr = r.hdr;
@@ -636,25 +637,25 @@ hipError_t launch_sstream(int op, int variant, bool fixed, const RunArgs &r, uin
   // 16 blocks per XCD
   a.order = (variant & 8) ? kOrderScatter : ((variant & 4) ? dev::kOrderDefault : 4u);
   uint64_t bytes = r.total_bytes;
-  uint64_t min_waves = (r.count + kMaxRun - 1) / kMaxRun;  // variable: <= kMaxRun images per run
+  uint64_t min_waves = (im.count + kMaxRun - 1) / kMaxRun;  // variable: <= kMaxRun images per run
   if (fixed) {
-    if (!sstream_fixed_applies(r.stride, r.len)) return hipErrorInvalidValue;
-    a.stride = static_cast<uint32_t>(r.stride);
-    a.len = r.len;
-    a.lead = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(r.arena) & 15u);  // the same for every image
-    a.nchunk = (a.lead + r.len + 15) >> 4;
+    if (!sstream_fixed_applies(im.stride, im.len)) return hipErrorInvalidValue;
+    a.stride = static_cast<uint32_t>(im.stride);
+    a.len = im.len;
+    a.lead = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(im.arena) & 15u);  // the same for every image
+    a.nchunk = (a.lead + im.len + 15) >> 4;
     uint32_t sh = 0;
     while ((2u << sh) <= a.nchunk) ++sh;  // floor(log2 nchunk)
     a.shift = sh;
     a.magic = (a.nchunk & (a.nchunk - 1)) == 0
                   ? 0u
                   : static_cast<uint32_t>(((uint64_t{1} << (32 + sh)) + a.nchunk - 1) / a.nchunk);
-    bytes = r.count * r.len;
+    bytes = im.count * im.len;
     // runs below 2^31 arena bytes and 2^27 compacted chunks (u32 run arithmetic)
-    const uint64_t per = std::min<uint64_t>((uint64_t{1} << 30) / r.stride, (uint64_t{1} << 26) / a.nchunk);
-    min_waves = (r.count + per - 1) / std::max<uint64_t>(per, 1);
+    const uint64_t per = std::min<uint64_t>((uint64_t{1} << 30) / im.stride, (uint64_t{1} << 26) / a.nchunk);
+    min_waves = (im.count + per - 1) / std::max<uint64_t>(per, 1);
   }
-  if (bytes == 0) bytes = r.count * 1024;
+  if (bytes == 0) bytes = im.count * 1024;
   // grid: M x the resident grid, M a power of two, blocks in the scattered
   // order (scripts/ss_sweep.py, scripts/sparse_probe.py; profiles/r02/
   // ss_sweep3_scatter.log, ss_sweep4_run128.log, sparse_probe2_orders.log).

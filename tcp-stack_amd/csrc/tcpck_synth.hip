@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "tcpck.h"
+#include "tcpck_internal.h"
 
 namespace {
 
@@ -56,14 +57,13 @@ __device__ inline uint16_t payload_word(uint64_t key, uint64_t m, int kind) {
   return static_cast<uint16_t>(splitmix64(key + (m >> 2)) >> (16 * (m & 3)));
 }
 
-__global__ void synth_kernel(uint8_t *arena, const uint64_t *offsets, const uint32_t *lengths,
-                             uint64_t stride, uint32_t flen, uint64_t count, uint64_t seed,
-                             uint64_t first_index, int kind, uint32_t words_per_image) {
+__global__ void synth_kernel(tcpck::ImageSpan im, uint64_t seed, uint64_t first_index, int kind,
+                             uint32_t words_per_image) {
   // grid: x over word index within an image (strided), y/z over images
   const uint64_t k = static_cast<uint64_t>(blockIdx.y) + static_cast<uint64_t>(blockIdx.z) * gridDim.y;
-  if (k >= count) return;
-  const uint64_t off = offsets ? offsets[k] : k * stride;
-  const uint32_t len = offsets ? lengths[k] : flen;
+  if (k >= im.count) return;
+  const uint64_t off = im.start(k);
+  const uint32_t len = im.length(k);
   const uint64_t idx = first_index + k;
   const uint64_t key = splitmix64(seed ^ (idx * 0xD1B54A32D192ED03ull));
   const uint32_t payload = len >= 32 ? len - 32 : 0;
@@ -72,13 +72,13 @@ __global__ void synth_kernel(uint8_t *arena, const uint64_t *offsets, const uint
        m += gridDim.x * blockDim.x) {
     const uint16_t w = m < 16 ? header_word(static_cast<int>(m), payload, seq)
                               : payload_word(key, m - 16, kind);
-    *reinterpret_cast<uint16_t *>(arena + off + 2ull * m) = w;
+    *reinterpret_cast<uint16_t *>(im.arena + off + 2ull * m) = w;
   }
 }
 
-int launch(void *d_arena, const uint64_t *d_off, const uint32_t *d_len, uint64_t stride, uint32_t flen,
-           uint32_t max_len, uint64_t count, uint64_t seed, uint64_t first, int kind,
+int launch(const tcpck::ImageSpan &im, uint32_t max_len, uint64_t seed, uint64_t first, int kind,
            tcpck_stream stream) {
+  const uint64_t count = im.count;
   if (count == 0) return TCPCK_OK;
   const uint32_t words = (max_len + 1) / 2;
   const uint32_t threads = 256;
@@ -89,9 +89,7 @@ int launch(void *d_arena, const uint64_t *d_off, const uint32_t *d_len, uint64_t
   if (gz > 65535) return TCPCK_EINVAL;
   (void)hipGetLastError();  // a stale error from an earlier failed call is not this launch's
   hipLaunchKernelGGL(synth_kernel, dim3(gx, static_cast<uint32_t>(gy), static_cast<uint32_t>(gz)),
-                     dim3(threads), 0, static_cast<hipStream_t>(stream),
-                     static_cast<uint8_t *>(d_arena), d_off, d_len, stride, flen, count, seed, first,
-                     kind, words);
+                     dim3(threads), 0, static_cast<hipStream_t>(stream), im, seed, first, kind, words);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? TCPCK_OK : TCPCK_EHIP - static_cast<int>(e);
 }
@@ -105,7 +103,8 @@ extern "C" {
 int tcpck_synth_fixed(void *d_arena, uint64_t stride, uint32_t len, uint64_t count, uint64_t seed,
                       uint64_t first_index, int kind, tcpck_stream stream) {
   if (!d_arena || (len & 1) || (stride & 1)) return TCPCK_EINVAL;
-  return launch(d_arena, nullptr, nullptr, stride, len, len, count, seed, first_index, kind, stream);
+  const tcpck::ImageSpan im{static_cast<uint8_t *>(d_arena), nullptr, nullptr, stride, 0, count, len};
+  return launch(im, len, seed, first_index, kind, stream);
 }
 
 // Variable-length synthetic batch over device offsets/lengths; max_len bounds lengths[k].
@@ -113,7 +112,8 @@ int tcpck_synth_var(void *d_arena, const uint64_t *d_offsets, const uint32_t *d_
                     uint32_t max_len, uint64_t count, uint64_t seed, uint64_t first_index, int kind,
                     tcpck_stream stream) {
   if (!d_arena || !d_offsets || !d_lengths) return TCPCK_EINVAL;
-  return launch(d_arena, d_offsets, d_lengths, 0, 0, max_len, count, seed, first_index, kind, stream);
+  const tcpck::ImageSpan im{static_cast<uint8_t *>(d_arena), d_offsets, d_lengths, 0, 0, count, 0};
+  return launch(im, max_len, seed, first_index, kind, stream);
 }
 
 }  // extern "C"

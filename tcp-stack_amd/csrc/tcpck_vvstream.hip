@@ -569,7 +569,8 @@ __global__ void __launch_bounds__(kBlock) vvstream_kernel(VVArgs a) {
 }
 
 template <int U, int OP, int SPLIT, int LAYOUT, bool KEEP = false, int MODE = kRef, bool BLK = false>
-hipError_t launch_one(const RunArgs &s, uint32_t oversub, int flags, uint32_t num_cus, hipStream_t stream) {
+hipError_t launch_one(const RunArgs &r, uint32_t oversub, int flags, uint32_t num_cus, hipStream_t stream) {
+  const ImageSpan &s = r.im;
   static const uint32_t per_cu = dev::resident_blocks_per_cu(vvstream_kernel<U, OP, SPLIT, LAYOUT, KEEP, MODE, BLK>);
   const uint64_t resident = static_cast<uint64_t>(per_cu) * num_cus;
   uint64_t blocks = resident * (oversub ? oversub : 1);
@@ -582,7 +583,7 @@ hipError_t launch_one(const RunArgs &s, uint32_t oversub, int flags, uint32_t nu
   a.lengths = s.lengths;
   a.base = s.base;
   a.count = s.count;
-  a.out = s.out;
+  a.out = r.out;
   a.per_wave = s.count / (blocks * kWavesPerBlock);
   a.rem = s.count % (blocks * kWavesPerBlock);
   a.stride = static_cast<uint32_t>(s.stride);
@@ -590,7 +591,7 @@ hipError_t launch_one(const RunArgs &s, uint32_t oversub, int flags, uint32_t nu
   a.order = (flags & 8) ? 4u : dev::kOrderDefault;  // groups of 16 blocks per XCD
   a.keep_first = (flags & 16) ? ((flags & 256) ? 2u : 1u) : 0u;
   a.defer_field = (flags & 64) ? 1u : 0u;
-  a.dbg = s.dbg;
+  a.dbg = r.dbg;
   hipLaunchKernelGGL((vvstream_kernel<U, OP, SPLIT, LAYOUT, KEEP, MODE, BLK>), dim3(static_cast<uint32_t>(blocks)),
                      dim3(kBlock), 0, stream, a);
   return hipGetLastError();
@@ -626,10 +627,11 @@ hipError_t dispatch(int op, const RunArgs &a, uint32_t oversub, int flags, uint3
 
 hipError_t launch_vvstream(int op, int variant, bool fixed, const RunArgs &a, uint32_t num_cus,
                            hipStream_t stream) {
-  if (a.count == 0) return hipSuccess;
-  if (fixed && (a.len == 0 || a.stride < a.len || a.stride > (1u << 24))) return hipErrorInvalidValue;
-  const bool gap = fixed && a.stride != a.len;
-  const uint64_t bytes = fixed ? a.count * a.stride : a.total_bytes;
+  const ImageSpan &im = a.im;
+  if (im.count == 0) return hipSuccess;
+  if (fixed && (im.len == 0 || im.stride < im.len || im.stride > (1u << 24))) return hipErrorInvalidValue;
+  const bool gap = fixed && im.stride != im.len;
+  const uint64_t bytes = fixed ? im.count * im.stride : a.total_bytes;
   uint32_t m = a.oversub ? a.oversub : 1;
   // 8: XCD-chunked run order; 16: L2-kept first line; 32: kFill reads every
   // step with the default cache policy (small images); 64: kFill writes the

@@ -119,8 +119,8 @@ hipError_t launch_seg(int op, int mode, bool fixed, SegShape shape, const SegArg
   if (g_record)
     add(" seg(op=%d mode=%d fixed=%d shape=%d arena=%s off=%s len=%s stride=%" PRIu64 " base=%" PRIu64 " count=%" PRIu64
         " out=%s flen=%u os=%u order=%u rot=%u cus=%u s=%s)",
-        op, mode, fixed, static_cast<int>(shape), PS(a.arena), PS(a.offsets), PS(a.lengths), a.stride, a.base, a.count,
-        PS(a.out), a.len, a.oversub, a.order, a.rot, num_cus, PS(s));
+        op, mode, fixed, static_cast<int>(shape), PS(a.im.arena), PS(a.im.offsets), PS(a.im.lengths), a.im.stride,
+        a.im.base, a.im.count, PS(a.out), a.im.len, a.oversub, a.order, a.rot, num_cus, PS(s));
   return hipSuccess;
 }
 
@@ -128,8 +128,8 @@ namespace {
 void add_run(const char *name, int op, int variant, int fixed, const RunArgs &a, uint32_t num_cus, hipStream_t s) {
   add(" %s(op=%d v=%d fixed=%d arena=%s off=%s len=%s stride=%" PRIu64 " flen=%u base=%" PRIu64 " count=%" PRIu64
       " out=%s os=%u tb=%" PRIu64 " bpc=%u mode=%d hdr=%s dbg=%s cus=%u s=%s)",
-      name, op, variant, fixed, PS(a.arena), PS(a.offsets), PS(a.lengths), a.stride, a.len, a.base, a.count, PS(a.out),
-      a.oversub, a.total_bytes, a.blocks_per_cu, a.mode, PS(a.hdr), PS(a.dbg), num_cus, PS(s));
+      name, op, variant, fixed, PS(a.im.arena), PS(a.im.offsets), PS(a.im.lengths), a.im.stride, a.im.len, a.im.base,
+      a.im.count, PS(a.out), a.oversub, a.total_bytes, a.blocks_per_cu, a.mode, PS(a.hdr), PS(a.dbg), num_cus, PS(s));
 }
 }  // namespace
 
@@ -177,14 +177,14 @@ hipError_t launch_segment(int mode, int variant, SegmentArgs a, uint32_t oversub
 hipError_t launch_set_ack(int mode, const AckArgs &a, uint32_t num_cus, hipStream_t s) {
   if (g_record)
     add(" set_ack(mode=%d arena=%s off=%s stride=%" PRIu64 " count=%" PRIu64 " acks=%s ack=%u out=%s cus=%u s=%s)", mode,
-        PS(a.arena), PS(a.offsets), a.stride, a.count, PS(a.acks), a.ack, PS(a.out), num_cus, PS(s));
+        PS(a.im.arena), PS(a.im.offsets), a.im.stride, a.im.count, PS(a.acks), a.ack, PS(a.out), num_cus, PS(s));
   return hipSuccess;
 }
 
 hipError_t launch_header_swap(const HeaderArgs &a, uint32_t num_cus, hipStream_t s) {
   if (g_record)
-    add(" header(arena=%s off=%s stride=%" PRIu64 " count=%" PRIu64 " out=%s bits=%u cus=%u s=%s)", PS(a.arena),
-        PS(a.offsets), a.stride, a.count, PS(a.out), a.store_bits, num_cus, PS(s));
+    add(" header(arena=%s off=%s stride=%" PRIu64 " count=%" PRIu64 " out=%s bits=%u cus=%u s=%s)", PS(a.im.arena),
+        PS(a.im.offsets), a.im.stride, a.im.count, PS(a.out), a.store_bits, num_cus, PS(s));
   return hipSuccess;
 }
 
@@ -192,8 +192,8 @@ hipError_t launch_patch_fields(const PatchArgs &a, uint32_t num_cus, hipStream_t
   if (g_record)
     add(" patch(arena=%s stride=%" PRIu64 " off=%s len=%s base=%" PRIu64 " count=%" PRIu64 " sums=%s lo=%" PRIu64
         " hi=%" PRIu64 " update=%u packed=%u form=%u bits=%u rev=%u cus=%u s=%s)",
-        PS(a.arena), a.stride, PS(a.offsets), PS(a.lengths), a.base, a.count, PS(a.sums), a.lo, a.hi, a.update, a.packed,
-        a.probe_form, a.store_bits, a.reverse, num_cus, PS(s));
+        PS(a.im.arena), a.im.stride, PS(a.im.offsets), PS(a.im.lengths), a.im.base, a.im.count, PS(a.sums), a.lo, a.hi,
+        a.update, a.packed, a.probe_form, a.store_bits, a.reverse, num_cus, PS(s));
   return hipSuccess;
 }
 
