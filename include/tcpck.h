@@ -574,6 +574,88 @@ int tcpck_batch_segment(tcpck_ctx *ctx, int mode, const void *d_payload, uint64_
                         uint32_t seg, const void *hdr, uint32_t seq0, void *d_images, uint64_t stride,
                         uint16_t *d_out, tcpck_stream stream);
 
+/* ---- zero-copy segmentation: headers only, many connections per launch ----
+ * tcpck_batch_segment writes every payload byte a second time, into the
+ * images.  A datagram can leave as two pieces instead (sendmmsg, one two-entry
+ * iovec per datagram): the finished header from here, the payload from the send
+ * stream itself, which the reference keeps until it is acknowledged anyway
+ * (TcpSendingBuffer::Ack, include/tcp-buffer.h:51-68).  What is built per
+ * segment is what the reference puts in front of the payload:
+ * GetAsTcpPacket's TcpLength (include/tcp-buffer.h:82-98), Estab's seq =
+ * snd_nxt, snd_nxt += len (src/state.cc:167-184), TcpHeaderH2N
+ * (include/socket-internal.h:186-199) and the checksum over header and payload
+ * (include/socket-manager.h:259-260).
+ *
+ * A send ring is many connections with a few segments each: one cut per
+ * connection, the segments of all cuts numbered in order.  d_payload is the
+ * arena the send streams lie in; a single connection is the case of one cut.
+ *
+ * tcpck_plan_cuts: plain host code, reentrant.  Checks every cut, fills
+ * `first` and returns the ring's length through n_seg.  TCPCK_EINVAL, nothing
+ * written: an offset that is not a multiple of 4; odd bytes; a range outside
+ * [0, payload_bytes); tmpl >= n_tmpl; a total above 2^31; n_seg NULL, h_cuts
+ * NULL with n_cuts > 0, a seg or payload_bytes the calls below refuse.
+ * Overlapping cuts are allowed: the arena is only read.
+ *
+ * tcpck_batch_segment_headers: for ring index g in [0, n_seg), c the cut with
+ * first_c <= g < first_c + ceil(bytes_c / seg), i = g - first_c and len =
+ * min(seg, bytes_c - i * seg):
+ *   d_hdr[32 g, 32 g + 32)  template tmpl_c (32 B at d_tmpl + 32 tmpl_c, network
+ *                           order, the kind tcpck_batch_segment takes as `hdr`)
+ *                           with TcpLength (bytes 10-11) = htons(len), seq
+ *                           (16-19) = htonl(seq0_c + i * seg) (u32, it wraps)
+ *                           and bytes 28-29 = the checksum of header || payload
+ *                           with that field zero, raw as the reference stores
+ *                           it (TCPCK_MODE_REF) or folded (TCPCK_MODE_RFC1071):
+ *                           bytes 0-31 of image i of tcpck_batch_segment(
+ *                           d_payload + offset_c, bytes_c, seg, template,
+ *                           seq0_c, ...);
+ *   d_pay_off[g], d_pay_len[g]  offset_c + i * seg and len: the iovec's second
+ *                           entry is d_payload + d_pay_off[g], d_pay_len[g];
+ *   d_out[g]                the checksum.
+ * d_pay_off, d_pay_len and d_out may each be NULL.  The device table is not
+ * trusted.  A cut counts only when it is *sound*: it breaks no clause of
+ * tcpck_plan_cuts, its segments lie in [0, n_seg), and a neighbour confirms its
+ * `first` -- the cut before it ends where it starts (cut 0: it starts at 0), or
+ * it ends where the cut after it starts (the last cut: at n_seg).  A planned
+ * table is sound throughout, and one cut damaged in any field takes out only
+ * its own segments.  A g no sound cut claims gets an all-zero header, offset 0,
+ * length 0 and checksum 0.  The results are exact for every sound cut of a
+ * table whose sound cuts lie in ring order (a planned table with any cuts
+ * damaged is one); for any other table each g gets zeros or the header of a
+ * sound cut that claims it.  Whatever the arrays hold, nothing outside [0,
+ * n_seg) of an output is written and nothing outside [0, payload_bytes) is
+ * read.
+ * seg a multiple of 4 in [16, 65532]; payload_bytes even; n_seg <= 2^31;
+ * d_payload 4-B, d_hdr and d_tmpl 16-B, d_cuts and d_pay_off 8-B, d_pay_len 4-B
+ * aligned.  n_seg == 0 is TCPCK_OK with nothing launched.  TCPCK_EINVAL, checked
+ * before any launch: ctx NULL, a bad mode, any of the above, with n_seg > 0 a
+ * NULL d_hdr, d_payload (payload_bytes > 0), d_cuts (n_cuts > 0) or d_tmpl
+ * (n_tmpl > 0).  Asynchronous on `stream`; nothing is allocated; no host
+ * synchronisation.
+ *
+ * tcpck_segment_headers: the same contract on host arrays: plain host C++,
+ * reentrant, no device.  The CPU fallback and the second implementation the
+ * device call is tested against. */
+typedef struct tcpck_send_cut {   /* 32 B, 8-B aligned: one connection's share of a send ring */
+  uint64_t offset;    /* first byte of the cut in d_payload; a multiple of 4          */
+  uint32_t bytes;     /* even; 0: the connection sends nothing this ring               */
+  uint32_t seq0;      /* snd_nxt: the sequence number of the cut's first byte          */
+  uint32_t tmpl;      /* index into d_tmpl of the connection's 32-B header template    */
+  uint32_t first;     /* ring index of the cut's first segment: the exclusive prefix
+                         of ceil(bytes / seg) over the cuts before it                  */
+  uint32_t reserved[2];
+} tcpck_send_cut;
+int tcpck_plan_cuts(tcpck_send_cut *h_cuts, uint32_t n_cuts, uint32_t seg, uint64_t payload_bytes,
+                    uint32_t n_tmpl, uint64_t *n_seg);
+int tcpck_batch_segment_headers(tcpck_ctx *ctx, int mode, const void *d_payload, uint64_t payload_bytes,
+                                uint32_t seg, const tcpck_send_cut *d_cuts, uint32_t n_cuts,
+                                const void *d_tmpl, uint32_t n_tmpl, uint64_t n_seg, void *d_hdr,
+                                uint64_t *d_pay_off, uint32_t *d_pay_len, uint16_t *d_out, tcpck_stream stream);
+int tcpck_segment_headers(int mode, const void *h_payload, uint64_t payload_bytes, uint32_t seg,
+                          const tcpck_send_cut *h_cuts, uint32_t n_cuts, const void *h_tmpl, uint32_t n_tmpl,
+                          uint64_t n_seg, void *h_hdr, uint64_t *h_pay_off, uint32_t *h_pay_len, uint16_t *h_out);
+
 /* ---- batched, host memory (end to end incl. PCIe) ------------------------
  * Segments start and end in host memory (the loopback/socket buffers of
  * network-service.cc / tcp-buffer.h).  The batch is split into chunks that are

@@ -12,6 +12,8 @@
 
 #include "tcpck_plan.h"
 
+struct tcpck_send_cut;  // include/tcpck.h
+
 namespace tcpck {
 
 enum Op : int { kChecksum = 0, kFill = 1, kVerify = 2 };
@@ -159,6 +161,25 @@ struct SegmentArgs {
 // stores; + 8 default block order (else XCD-chunked).  oversub: 0 = by size
 hipError_t launch_segment(int mode, int variant, SegmentArgs a, uint32_t oversub, uint32_t num_cus,
                           hipStream_t stream);
+// ---- segment headers (tcpck_segment_hdr.hip): a send ring of many connections
+// -> one finished header per segment, the payload checksummed where it lies ----
+struct SegmentHdrArgs {
+  const uint8_t *payload;        // the send arena (4-B aligned), only read
+  uint64_t payload_bytes;        // even
+  const tcpck_send_cut *cuts;    // the cut table (device, untrusted: tcpck_segment_hdr.h `sound`)
+  const uint8_t *tmpl;           // 32-B network-order header templates (16-B aligned)
+  uint8_t *hdr;                  // output: header g at 32 g (16-B aligned)
+  uint64_t *pay_off;             // outputs, each may be null: the payload's offset,
+  uint32_t *pay_len;             //   its length,
+  uint16_t *out;                 //   the checksum
+  uint64_t n_seg;                // ring length, <= 2^31
+  uint64_t per_wave, rem;        // run split in groups of 4 ring indices, set by the launcher
+  uint32_t n_cuts, n_tmpl;
+  uint32_t seg;                  // % 4 == 0, in [16, 65532]
+  uint32_t magic, shift;         // set by the launcher: x / seg for x < 2^31
+  uint32_t order;                // block order, set by the launcher
+};
+hipError_t launch_segment_headers(int mode, SegmentHdrArgs a, uint32_t num_cus, hipStream_t stream);
 // ---- deliver (tcpck_deliver.hip): accepted payloads -> the receive stream ----
 // Image k's payload (bytes 32..) goes to recv[dst[k], ...) unless dst[k] is
 // TCPCK_DELIVER_SKIP, odd, or the range does not fit recv_bytes.

@@ -149,6 +149,7 @@ EXPORTS = (
     "tcpck_plan_deliver_multi",
     "tcpck_reply_scratch_bytes", "tcpck_batch_reply", "tcpck_build_replies",
     "tcpck_resend_scratch_bytes", "tcpck_batch_resend", "tcpck_resend_images",
+    "tcpck_plan_cuts", "tcpck_batch_segment_headers", "tcpck_segment_headers",
 )
 
 
@@ -253,6 +254,9 @@ def lib(probe: bool = False) -> ctypes.CDLL:
                                      vp, vp, vp]),
         "tcpck_resend_images": (i32, [i32, i32, vp, u64, u64, u32, vp, vp, vp, vp, u32, u64, vp, vp, vp, vp, vp, u64,
                                       ctypes.POINTER(u64)]),
+        "tcpck_plan_cuts": (i32, [vp, u32, u32, u64, u32, ctypes.POINTER(u64)]),
+        "tcpck_batch_segment_headers": (i32, [vp, i32, vp, u64, u32, vp, u32, vp, u32, u64, vp, vp, vp, vp, vp]),
+        "tcpck_segment_headers": (i32, [i32, vp, u64, u32, vp, u32, vp, u32, u64, vp, vp, vp, vp]),
         # include/tcpck_tuning.h
         "tcpck_batch_fixed_ex": (i32, [vp, i32, i32, vp, u64, u32, u64, vp, i32, i32, vp]),
         "tcpck_batch_var_ex": (i32, [vp, i32, i32, vp, vp, vp, u64, vp, ctypes.POINTER(Layout), i32, i32, vp]),
@@ -493,6 +497,45 @@ def resend_images(arena, snd, count: int | None = None, stride: int = 0, length:
     return keep[:n], out_off[:w], out_len[:w], out_conn[:w], src[:w], total.value
 
 
+def send_cut_dtype():
+    """tcpck_send_cut as a numpy structured dtype (32 B): one connection's share of a send ring."""
+    import numpy as np
+    return np.dtype([("offset", "<u8"), ("bytes", "<u4"), ("seq0", "<u4"), ("tmpl", "<u4"), ("first", "<u4"),
+                     ("reserved", "<u4", (2,))])
+
+
+def plan_cuts(cuts, seg: int, payload_bytes: int, n_tmpl: int) -> int:
+    """tcpck_plan_cuts (host only): checks every cut of a send ring -- a numpy array of send_cut_dtype()
+    with offset, bytes, seq0 and tmpl set -- fills `first` in place and returns the ring's length in
+    segments of at most `seg` bytes."""
+    if cuts.dtype != send_cut_dtype() or not cuts.flags.c_contiguous:
+        raise ValueError("cuts must be a contiguous array of send_cut_dtype()")
+    n = ctypes.c_uint64()
+    _check(lib().tcpck_plan_cuts(cuts.ctypes.data if cuts.size else None, cuts.size, seg, payload_bytes, n_tmpl,
+                                 ctypes.byref(n)), "tcpck_plan_cuts")
+    return n.value
+
+
+def segment_headers(payload, seg: int, cuts, tmpl, n_seg: int, mode: int = MODE_REF):
+    """tcpck_segment_headers on numpy arrays (host only, no device): zero-copy segmentation of a send
+    ring.  payload: the send arena (uint8); cuts: the planned table (send_cut_dtype()); tmpl: 32 B of
+    network-order header per connection.  Returns (hdr u8[n_seg, 32], pay_off u64[n_seg], pay_len
+    u32[n_seg], checksums u16[n_seg]): segment g leaves as hdr[g] followed by payload[pay_off[g]:
+    pay_off[g] + pay_len[g]]."""
+    import numpy as np
+    payload = np.ascontiguousarray(payload, dtype=np.uint8)
+    tmpl = np.require(np.ascontiguousarray(tmpl, dtype=np.uint8).reshape(-1), requirements=["ALIGNED"])
+    if tmpl.size % 32 or tmpl.ctypes.data % 16:
+        raise ValueError("tmpl must hold 32 bytes per connection, 16-B aligned")
+    hdr = np.zeros((n_seg + 1, 32), np.uint8)  # (one record more: never an empty array's NULL)
+    off, ln, cs = np.zeros(n_seg + 1, np.uint64), np.zeros(n_seg + 1, np.uint32), np.zeros(n_seg + 1, np.uint16)
+    _check(lib().tcpck_segment_headers(mode, payload.ctypes.data if payload.size else None, payload.size, seg,
+                                       cuts.ctypes.data if cuts.size else None, cuts.size,
+                                       tmpl.ctypes.data if tmpl.size else None, tmpl.size // 32, n_seg, hdr.ctypes.data,
+                                       off.ctypes.data, ln.ctypes.data, cs.ctypes.data), "tcpck_segment_headers")
+    return hdr[:n_seg], off[:n_seg], ln[:n_seg], cs[:n_seg]
+
+
 class ConnTable:
     """tcpck_conn_table: ReceivePacket's socket map (socket-manager.h:187-196, 235-245) as a host
     mirror plus a device image batch_demux probes.  Keys are (host_port, peer_ip, peer_port), a
@@ -687,6 +730,17 @@ class Context:
         else:
             _check(self._L.tcpck_batch_segment_ex(*args, param, _stream(stream)), "tcpck_batch_segment_ex")
         return (payload_bytes + seg - 1) // seg
+
+    def batch_segment_headers(self, payload, payload_bytes: int, seg: int, cuts, n_cuts: int, tmpl, n_tmpl: int,
+                              n_seg: int, hdr, pay_off=None, pay_len=None, out=None, mode: int = MODE_REF,
+                              stream=None) -> None:
+        """Zero-copy segmentation of a send ring (tcpck_batch_segment_headers): device arrays; cuts = the
+        table plan_cuts filled (32 B per connection), tmpl 32 B per template; header g at hdr + 32 g with
+        TcpLength, seq and the checksum over header and payload set, pay_off[g] (u64) / pay_len[g] (u32)
+        where the payload lies in `payload`, out[g] (u16) the checksum (each may be None)."""
+        _check(self._L.tcpck_batch_segment_headers(self._h, mode, _ptr(payload), payload_bytes, seg, _ptr(cuts), n_cuts,
+                                                   _ptr(tmpl), n_tmpl, n_seg, _ptr(hdr), _ptr(pay_off), _ptr(pay_len),
+                                                   _ptr(out), _stream(stream)), "tcpck_batch_segment_headers")
 
     # explicit kernel choice (include/tcpck_tuning.h)
     def batch_fixed_ex(self, op: int, arena, stride: int, length: int, count: int, out, kernel: int,
